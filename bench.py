@@ -19,13 +19,20 @@ the coefficients, chunked so that chunk i's gather overlaps chunk i+1's solve  =
 the metric is quoted on], 3 = 125k of the same (1M over 8 GPUs), 4 = the mixed request (N in {8, 10, 12} x K in {4, 8, 16,
 32}, D = 3: 12 buckets x 2500 = 30k trajectories per step, ONE cross-structure launch per step through mtg_multi_solve),
 5 = 12.5k x (K=16, N=10, D=4, velocity + acceleration fixed at interior vertices; 100k over 8 GPUs).
-The default run (config 2) also times the SURVEY 8(f) rows -- sampling, extrema / time scaling, Mellinger cost + gradient --
-as `extra.next` (`--no-next` skips them).
 
-Prints ONE JSON line (rank 0).  `roofline.achieved` = algorithmic bytes (8*(K + D*n_fixed + K*D*N) per
-trajectory) of the timed steps / their duration on the device, measured with HIP events recorded by the library on the
-launch stream immediately around the SAME launches that `value` comes from.  `cpu_baseline` = the reference algorithm's
-CPU restatement (oracle/, the checker -- never the product path) timed on this box's host cores.
+A plain run does only what the headline figure needs: set-up (buffer sets, one touch of each, one untimed run of the
+warm-up + timed region, the --settle-ms phase), the warm-up steps, the timed steps, `--dump-outputs DIR` (the coefficients
+the LAST timed step wrote, rank 0, as DIR/<name>.npy; same arguments => same inputs), the line.  `--full` adds everything
+else: cold_start (that untimed run, reported) and, after the timed steps, parity of the timed launch's outputs vs the
+oracles, sustained, value_other_form, value_aos_inputs, `extra` (config 2: the SURVEY 8(f) rows -- sampling, extrema / time
+scaling, Mellinger cost + gradient -- as `extra.next`, `--no-next` skips them), the live PMC traffic, the N > 1 gather and
+cpu_baseline.
+
+Prints ONE JSON line (rank 0).  `ms_per_step` = wall clock of the timed region / --steps.  `roofline.achieved` = algorithmic
+bytes (8*(K + D*n_fixed + K*D*N) per trajectory) of the timed steps / their duration on the device, measured
+with HIP events recorded by the library on the launch stream immediately around the SAME launches that `value` comes from.
+`cpu_baseline` (--full) = the reference algorithm's CPU restatement (oracle/, the checker -- never the product path) timed on
+the host cores.
 """
 import argparse
 import ctypes
@@ -92,7 +99,7 @@ def parse_args(argv=None):
                     "exercise the multi-process path on a box with fewer GPUs than ranks)")
     ap.add_argument("--same-device", action="store_true", help="all ranks on HIP device 0 (multi-process tests on a 1-GPU box)")
     ap.add_argument("--plumbing-only", action="store_true", help="spawn / rendezvous / reduce only, no GPU work (CPU test)")
-    ap.add_argument("--extra", action="store_true", help="also time the 1M per-launch batch and the host-pointer paths")
+    ap.add_argument("--extra", action="store_true", help="(--full) also time the 1M per-launch batch and the host-pointer paths")
     ap.add_argument("--sequence", default="queue", choices=["queue", "launches"],
                     help="how the library runs the K independent batches of the timed region: 'queue' = one persistent launch "
                          "over all of them (throughput form), 'launches' = one kernel launch per batch (latency form)")
@@ -110,6 +117,14 @@ def parse_args(argv=None):
                          "report each repeat's host-clock breakdown (extra.timed_region_repeats); never part of `value`")
     ap.add_argument("--no-extras", action="store_true",
                     help="only the timed steps (profiling runs: the kernel statistics then cover the same launches as the metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: cold_start, parity of the timed launch vs "
+                         "the oracles, sustained, the other hand-over form and input layout, the extra rows, the live PMC traffic, "
+                         "the N > 1 gather and the CPU baseline.  Without it a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the LAST timed step (rank 0) as DIR/<name>.npy (float64; "
+                         "a fixed, seeded sample of rows when they exceed 60 MB in all)")
     return ap.parse_args(argv)
 
 
@@ -497,6 +512,32 @@ class MixedLoop:
         return [b["coeffs"] for s in self.sets for b in s]
 
 
+DUMP_BYTES = 60_000_000   # --dump-outputs: at most this many bytes in all (60 MB < 64 MB)
+DUMP_SEED = 20261016      # the fixed row sample of outputs larger than that
+
+
+def last_step_outputs(named):
+    """--dump-outputs: {name: device tensor [B][...]} of the last timed step -> {name: host float64 array}.  Where the arrays
+    exceed DUMP_BYTES in all, each keeps the same share of its rows, a sorted sample drawn with DUMP_SEED (a function of the
+    shapes only: two builds run with the same arguments dump the same rows)."""
+    import torch
+    total = sum(t.numel() * 8 for t in named.values())
+    out = {}
+    for name, t in named.items():
+        if total > DUMP_BYTES:
+            rows = max(1, (t.shape[0] * DUMP_BYTES) // total)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.shape[0], size=rows, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        out[name] = t.to(torch.float64).cpu().numpy()
+    return out
+
+
+def write_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 FP64_VALU_PEAK = {"simds": 1024, "clock_hz": 2.4e9, "cycles_per_wave_instruction": 4.0, "tflops": 78.6}
 
 
@@ -646,6 +687,8 @@ def main():
         rank_devices = [int(x.item()) for x in dv]
         assert ranks_seen == world
 
+    full = args.full                          # everything beside the headline figure (module docstring)
+    extras = full and not args.no_extras
     cfg = CONFIGS[args.config]
     if args.layout is None:
         args.layout = "soa16" if args.config == 5 else "soa"
@@ -743,7 +786,7 @@ def main():
         settle_within = max(1, min(args.warmup, nsets)) if (args.settle_ms > 0 and not mixed) else None
         # (built BEFORE the settle phase: no host work may sit between that phase and the contract's warm-up + timed steps)
         parity = None
-        if rank == 0 and not args.no_parity:
+        if full and rank == 0 and not args.no_parity:
             # (config 4: >= 512 sampled trajectories per polynomial order)
             parity = ParitySample(nsets, args.steps, args.warmup, args.parity_samples * (3 if mixed else 1),
                                   settle_sets=range(settle_within or 0))
@@ -767,12 +810,14 @@ def main():
             # A fresh process starts on a GPU that has just come out of idle (rocm-smi: sclk level 543 MHz); the contract's W
             # warm-up steps are ~30 us of work, and the first timed region then runs 10-15 % slower than every later one
             # (tools/gpu_r3_t.sh: 98-102 us vs 87-91 us per 20-batch launch).  Reported, not hidden: the same warm-up + timed
-            # region is run ONCE before the settle phase and kept as `cold_start` in the line; then the device is kept busy
-            # with the same work for settle_ms (set-up, not a step), then the contract's warm-up + timed steps follow.
+            # region is run ONCE before the settle phase and kept as `cold_start` in the line (a plain run: set-up, not reported);
+            # then the device is kept busy with the same work for settle_ms (set-up, not a step), then the contract's warm-up +
+            # timed steps follow.
             dt_c, us_c = timed(loop, args.steps, args.warmup)
-            cold = {"kernel_us_per_step": us_c, "frac": bytes_per_step / us_c * 1e-3 / HBM_PEAK_GBS, "wall_us": dt_c * 1e6,
-                    "units_per_s_this_rank": traj_per_step * args.steps / dt_c, "wall_breakdown_us": dict(stamps["breakdown_us"]),
-                    "is": "the same warm-up + timed region, run once BEFORE the settle phase: what a process that starts on an idle GPU sees first"}
+            if full:
+                cold = {"kernel_us_per_step": us_c, "frac": bytes_per_step / us_c * 1e-3 / HBM_PEAK_GBS, "wall_us": dt_c * 1e6,
+                        "units_per_s_this_rank": traj_per_step * args.steps / dt_c, "wall_breakdown_us": dict(stamps["breakdown_us"]),
+                        "is": "the same warm-up + timed region, run once BEFORE the settle phase: what a process that starts on an idle GPU sees first"}
             if settle_within and parity is not None and not parity.after_warmup:
                 parity.prefill()
                 prefilled = True
@@ -785,10 +830,17 @@ def main():
         dt, step_us = timed(loop, args.steps, args.warmup, parity, prefilled)
         wall_breakdown = dict(stamps["breakdown_us"])
         ctx.sync()  # raises if any trajectory flagged bad time / singular
+        if args.dump_outputs and rank == 0:
+            # what the last timed step wrote, before anything else rewrites the buffers (its buffer set in the rotation)
+            last = (args.warmup + args.steps - 1) % nsets
+            write_outputs(args.dump_outputs, last_step_outputs(
+                {f"coeffs_N{b['n_coeffs']}_K{len(b['masks']) - 1}": b["coeffs"] for b in loop.sets[last]} if mixed
+                else {"coeffs": sets[last][2]}))
         if parity is not None:
             parity.collect()    # the sampled rows of the TIMED launch's outputs, before anything else rewrites the buffers
-        for co in (loop.outputs() if mixed else [x[2] for x in sets]):
-            assert torch.isfinite(co).all()
+        if full:
+            for co in (loop.outputs() if mixed else [x[2] for x in sets]):
+                assert torch.isfinite(co).all()
 
         extra, fill_us, peer = {}, None, None
         # ---- `sustained` (round 6, first-class field): the same queue launches, continuously for >= --sustained-seconds over the
@@ -796,7 +848,7 @@ def main():
         # clock is probed next to them by a one-wave kernel on its own stream (s_memtime against the 100 MHz s_memrealtime:
         # include/mtg_hip_lab.h) -- the FP64-heavy kernels run power-limited, which a 90-us burst after a 50-ms settle does not show
         sustained = None
-        if args.sustained_seconds > 0 and not args.no_extras and not per_batch:
+        if args.sustained_seconds > 0 and extras and not per_batch:
             chunk = min(96, nsets) if not mixed else min(16, nsets)
             est_us = max(step_us, 0.5) * chunk
             calls = max(8, int(args.sustained_seconds * 1e6 / est_us) + 1)
@@ -836,7 +888,7 @@ def main():
         # ---- the queue form on AoS inputs (times[B][K], d_fixed[B][D][n_fixed]: the order a reference-side caller's Vertex::Vector
         # packs into), same protocol as value_other_form: W warm-up + K timed steps, wall clock
         aos_peer = None
-        if rank == 0 and not args.no_extras and not mixed and args.layout != "aos":
+        if rank == 0 and extras and not mixed and args.layout != "aos":
             try:
                 aos_sets = []
                 for (t_, f_, co_) in sets:
@@ -862,7 +914,7 @@ def main():
                 dt_r, us_r = timed(loop, args.steps, args.warmup)
                 reps_.append(dict(stamps["breakdown_us"], device_us_per_step=us_r))
             extra["timed_region_repeats"] = reps_
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and extras:
             # The OTHER hand-over form of the same K steps under the same protocol (W warm-up steps, K timed steps, wall clock
             # around them), reported as a PEER of `value`: one kernel launch per step (what a caller whose batches arrive one
             # at a time gets) when `value` is the queue form, and vice versa.
@@ -878,7 +930,7 @@ def main():
                            "batches arrive one at a time can reproduce (this rank's clock)") if not per_batch else
                           "the K steps handed to the library together (one persistent launch per <= 96 steps)"}
             del other
-        if rank == 0 and not args.no_extras and mixed:
+        if rank == 0 and extras and mixed:
             us, wall = side_run(loop, 96, warm=16)
             extra["rotating_buffers_96_steps"] = side_entry(us, wall, 96, nsets)
             other = MixedLoop(m, ctx, B, nsets, dev, 1234 + rank, per_step_call=not per_batch)
@@ -887,7 +939,7 @@ def main():
             extra["one_launch_per_request" if not per_batch else "requests_merged_into_one_launch"] = dict(
                 side_entry(us, wall, 96, nsets), note="one mtg_multi_solve call (one cross-structure launch) per mixed request"
                 if not per_batch else "the 96 requests as one 12 x 96-item request")
-        if rank == 0 and not args.no_extras and not mixed:
+        if rank == 0 and extras and not mixed:
             big = set_bytes * nsets > 8 * 2**30          # config 3: keep the extras short
             long_steps = 200 if big else 2000
             # the other form of the same loop: one launch per batch (latency form) when `value` is the queue, and vice versa
@@ -949,7 +1001,7 @@ def main():
                     del tb, fb, cb
             if args.config == 2 and not args.no_next and args.layout != "soa16":
                 extra["next"] = next_rows(m, ctx, plan, sets, B, K, D, N)
-        if args.extra and rank == 0 and args.config == 2:
+        if full and args.extra and rank == 0 and args.config == 2:
             # host buffers in / out (MTG_FLAG_HOST_POINTERS): PCIe-inclusive rate, never the reported value.
             t, f, _ = sets[0]
             th = (t[:, :B].t().contiguous() if args.layout != "aos" else t).cpu()
@@ -964,7 +1016,7 @@ def main():
                 extra[f"host_pointers_{tag}_pcie_inclusive_traj_per_s"] = 5 * B / (time.perf_counter() - t1)
 
         gather = None
-        if grouped and not args.no_gather and not mixed:
+        if full and grouped and not args.no_gather and not mixed:
             # solve + final all_gather of the coefficients: chunked, chunk i's gather overlaps chunk i+1's
             # solve; reported beside the solve-only number, never part of `value`
             from mav_trajectory_generation_amd import dist as mdist
@@ -1108,13 +1160,13 @@ def main():
                       + (" (SoA, row stride padded to a multiple of 16 trajectories: mtg_layout_soa_padded)" if args.layout == "soa16" else "")
                       + ", coeffs [B][K][D][N]")
         traffic_prof = None
-        if world == 1 and not args.no_live_traffic and not args.no_extras:
+        if world == 1 and not args.no_live_traffic and extras:
             traffic_prof = live_traffic(args, B)
         if traffic_prof is None:
             traffic_prof = profile_traffic(traj_per_step, args.config, args.steps, args.warmup)
         if args.settle_ms > 0:
             what += (f"; set-up before the contract's warm-up + timed steps: {args.settle_ms:g} ms of the same work (a fresh process "
-                     f"starts on an idle GPU; the timed region measured before that phase is reported as cold_start)"
+                     f"starts on an idle GPU" + ("; the timed region measured before that phase is reported as cold_start)" if cold else ")")
                      + (f", as {nsets}-batch calls rotating over the warm-up's {settle_within} buffer set(s)" if settle_within else ""))
         out = {
             "metric": {2: "trajectories/sec (8-seg, N=10, 3D min-snap solveLinear)",
@@ -1178,7 +1230,7 @@ def main():
             out["extra"] = extra
         if gather is not None:
             out["gather"] = gather
-    if not args.no_cpu_baseline and args.config == 2:
+    if full and not args.no_cpu_baseline and args.config == 2:
         # rank 0's host cores, after every GPU measurement (the other ranks wait in the barrier below)
         if rank == 0:
             out["cpu_baseline"] = cpu_baseline(200_000, 4321)

@@ -44,7 +44,7 @@ def test_world_size_mismatch_fails_loudly():
 @pytest.mark.gpu
 def test_two_rank_bench_on_one_gpu():
     r = run_bench("--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "10", "--warmup", "3", "--batch", "4000",
-                  "--buffer-sets", "2", "--no-cpu-baseline", "--gather-chunks", "2")
+                  "--buffer-sets", "2", "--no-cpu-baseline", "--gather-chunks", "2", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     out = last_json(r.stdout)
     assert out["n_gpus"] == 2 and out["steps"] == 10 and out["scaling"] == "weak"
@@ -69,7 +69,7 @@ def test_rccl_branches_run_on_a_one_rank_group(launcher):
     box's one device (a one-rank group): everything but the cross-device transport itself.  launcher=True: under the very
     command the driver uses for N > 1 (python -m torch.distributed.run ... bench.py --gpus N), with N = 1."""
     argv = ["--gpus", "1", "--exercise-collectives", "--steps", "6", "--warmup", "2", "--batch", "4000", "--buffer-sets", "2",
-            "--no-cpu-baseline", "--no-extras", "--gather-chunks", "2"]
+            "--no-cpu-baseline", "--no-extras", "--gather-chunks", "2", "--full"]
     if launcher:
         e = dict(os.environ)
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -100,7 +100,8 @@ def test_watchdog_falls_back_when_the_second_communicator_cannot_be_set_up():
     import time
     t0 = time.time()
     r = run_bench("--gpus", "1", "--exercise-collectives", "--steps", "6", "--warmup", "2", "--batch", "4000", "--buffer-sets", "2",
-                  "--no-cpu-baseline", "--no-extras", "--gather-chunks", "2", "--mtg-comm-init-timeout", "3", env={"MTG_BENCH_TEST_COMM_HANG": "1"})
+                  "--no-cpu-baseline", "--no-extras", "--gather-chunks", "2", "--mtg-comm-init-timeout", "3", "--full",
+                  env={"MTG_BENCH_TEST_COMM_HANG": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     assert time.time() - t0 < 300
     out = last_json(r.stdout)
@@ -112,7 +113,7 @@ def test_watchdog_falls_back_when_the_second_communicator_cannot_be_set_up():
 @pytest.mark.gpu
 def test_two_rank_bench_carries_the_cpu_baseline():
     r = run_bench("--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "4", "--warmup", "2", "--batch", "2000",
-                  "--buffer-sets", "2", "--no-gather", "--no-extras")
+                  "--buffer-sets", "2", "--no-gather", "--no-extras", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     out = last_json(r.stdout)
     assert out["n_gpus"] == 2 and out["cpu_baseline"]["value"] > 0 and out["cpu_baseline"]["cores"] >= 1
@@ -120,7 +121,7 @@ def test_two_rank_bench_carries_the_cpu_baseline():
 
 @pytest.mark.gpu
 def test_single_gpu_bench_line_has_the_contract_fields():
-    r = run_bench("--steps", "20", "--warmup", "5", "--no-cpu-baseline")
+    r = run_bench("--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     out = last_json(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -178,7 +179,7 @@ def test_latency_form_and_config4_lines():
     out = last_json(r.stdout)
     assert out["config"]["sequence"] == "launches" and out["roofline"]["launches"] == 20
     assert out["roofline"]["bytes_per_launch"] == 10_000 * 2392
-    r = run_bench("--config", "4", "--steps", "10", "--warmup", "3", "--buffer-sets", "4")
+    r = run_bench("--config", "4", "--steps", "10", "--warmup", "3", "--buffer-sets", "4", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     out = last_json(r.stdout)
     # 12 buckets x 2500: sum over buckets of 8 * (K + 3 (N + K - 1) + 3 K N) bytes per trajectory = 128.9 MB per step
@@ -202,3 +203,46 @@ def test_latency_form_and_config4_lines():
     assert rb["inside_timed_region"] and 0 < rb["mtg_multi_create_us"] <= rb["host_us"]
     assert rb["share_of_timed_region_wall"] <= 0.25, rb
     assert out["value_other_form"]["sequence"] == "launches" and out["value_other_form"]["value"] > 0
+
+
+def test_plain_and_full_options_are_there():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) measures only the headline figure; --dump-outputs writes the coefficients the LAST timed step
+    wrote, the same from run to run, and they are what the library computes for that step's inputs."""
+    import numpy as np
+    outs = []
+    for run in ("a", "b"):
+        r = run_bench("--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / run))
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = last_json(r.stdout)
+        assert out["steps"] == 7 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f64"
+        assert abs(out["value"] - 10_000 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+        for k in ("parity", "cpu_baseline", "extra", "gather"):
+            assert k not in out, k
+        assert out["cold_start"] is None and out["sustained"] is None and out["value_other_form"] is None
+        assert sorted(os.listdir(tmp_path / run)) == ["coeffs.npy"]
+        outs.append(np.load(tmp_path / run / "coeffs.npy"))
+    assert outs[0].dtype == np.float64 and outs[0].shape == (10_000, 8, 3, 10) and np.isfinite(outs[0]).all()
+    assert np.array_equal(outs[0], outs[1])
+    # the last of the 2 + 7 steps used buffer set 8 of the rotation (>= 16 sets): seed 1234 + 1000 * 8, SoA inputs
+    import torch
+    import mav_trajectory_generation_amd as m
+    masks = m.ends_full_masks(10, 8)
+    ctx = m.Context(0)
+    plan = m.Plan(ctx, 10, 3, 8, 4, masks)
+    t, f = m.random_waypoint_batch(10_000, 8, 3, 10, masks, seed=1234 + 1000 * 8, device="cuda", layout="soa")
+    co, _, _ = plan.solve(t, f, layout="soa")
+    ctx.sync()
+    want = co.cpu().numpy()
+    plan.close()
+    ctx.close()
+    assert np.abs(outs[0] - want).max() <= 1e-9 * np.abs(want).max()

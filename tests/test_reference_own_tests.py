@@ -11,7 +11,7 @@ import subprocess
 
 import pytest
 
-BIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_tests", "bin")
+BIN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "ref_tests")   # (built with the other reference builds)
 FILTER = "--gtest_filter=-*UnconstrainedNonlinear*:*.TimeScaling/*"
 
 

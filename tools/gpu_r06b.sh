@@ -6,10 +6,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/r06b; mkdir -p $OUT
 cd $R
 timeout 900 python -m pytest tests -m gpu -q -n 4 > $OUT/pytest_gpu.txt 2>&1; tail -n 30 $OUT/pytest_gpu.txt | cut -c1-400
-timeout 400 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.err
-timeout 300 python bench.py --gpus 2 --backend gloo --same-device --steps 20 --warmup 5 --no-cpu-baseline 2>$OUT/bench2.err | grep "^{" > $OUT/bench_two_ranks_one_gpu.json
-timeout 300 python bench.py --gpus 1 --exercise-collectives --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>$OUT/bench3.err | grep "^{" > $OUT/bench_one_rank_rccl.json
-timeout 300 python bench.py --config 5 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_config5.json 2>> $OUT/bench.err
+timeout 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench.err; tail -c 300 $OUT/bench.err
+timeout 300 python bench.py --full --gpus 2 --backend gloo --same-device --steps 20 --warmup 5 --no-cpu-baseline 2>$OUT/bench2.err | grep "^{" > $OUT/bench_two_ranks_one_gpu.json
+timeout 300 python bench.py --full --gpus 1 --exercise-collectives --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>$OUT/bench3.err | grep "^{" > $OUT/bench_one_rank_rccl.json
+timeout 300 python bench.py --full --config 5 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_config5.json 2>> $OUT/bench.err
 for f in bench_driver_args bench_two_ranks_one_gpu bench_one_rank_rccl bench_config5; do
   python - $OUT/$f.json <<'PY'
 import json, sys

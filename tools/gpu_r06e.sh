@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/r06e; mkdir -p $OUT
 cd $R
 timeout 600 python -m pytest tests/test_refine.py tests/test_bench.py -m gpu -q -n 2 > $OUT/pytest_new.txt 2>&1; tail -n 12 $OUT/pytest_new.txt | cut -c1-400
-( time timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench.err ) 2>&1 | tail -3
+( time timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench.err ) 2>&1 | tail -3
 python - $OUT/bench_driver_args.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
