@@ -27,6 +27,9 @@ class TrajectoryBatch {
   int N() const { return N_; }
   int K() const { return K_; }
   int D() const { return D_; }
+  // the device copy, for the other batched entries of the C ABI (mav_trajectory_generation_ros/feasibility_analytic.h)
+  const double* deviceCoefficients() const { return coeffs_; }   // [B][K][D][N]
+  const double* deviceTimes() const { return times_; }           // [B][K]
 
   // Per-trajectory extrema of the derivative's magnitude over `dimensions` (Trajectory::computeMinMaxMagnitude).
   bool computeMinMaxMagnitude(int derivative, const std::vector<int>& dimensions, std::vector<Extremum>* minima,

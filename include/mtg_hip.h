@@ -346,6 +346,67 @@ int mtg_scale_segment_times_to_meet_constraints(mtg_context* ctx, int32_t n_coef
                                                 double a_max, int32_t max_iterations, double* workspace,
                                                 double* scaling, int32_t* within_range);
 
+/* ---- next step after the path: batched analytic input-feasibility check --------------------- */
+/* Replaces, for a batch, FeasibilityAnalytic::checkInputFeasibility(const Segment&) and
+ * FeasibilityBase::checkInputFeasibilityTrajectory (mav_trajectory_generation_ros/src/feasibility_analytic.cpp:42-233,
+ * feasibility_base.cpp:97-107): which trajectories can the vehicle fly under up to six input limits.
+ * A limit that is NaN is absent and its check is not computed; the others enter by magnitude (InputConstraints::
+ * addConstraint stores |value|).  mtg_input_constraints_init: no limits, min_section_time_s 0.05, gravity 9.81;
+ * ..._set_defaults: the reference's default limits (0.5 g, 1.5 g, 3.0, pi/2, pi/2, 2 pi).                       */
+typedef struct mtg_input_constraints {
+  double f_min, f_max;        /* thrust ||a + (0, 0, gravity)|| (mass-normalised, m/s^2)                         */
+  double v_max;               /* ||velocity||                                                                    */
+  double omega_xy_max;        /* roll/pitch rate: Mueller's bound sqrt(max jerk / min thrust) per section        */
+  double omega_z_max;         /* |yaw rate| (dimension 3, D == 4 only)                                           */
+  double omega_z_dot_max;     /* |yaw acceleration|                                                              */
+  double min_section_time_s;  /* FeasibilityAnalytic::Settings: shortest section the roll/pitch split examines   */
+  double gravity;             /* mav_msgs::kGravity upstream                                                     */
+} mtg_input_constraints;
+void mtg_input_constraints_init(mtg_input_constraints* constraints);
+void mtg_input_constraints_set_defaults(mtg_input_constraints* constraints);
+
+/* Result codes: the reference's enum InputFeasibilityResult (feasibility_base.h:34-50).  The analytic check never
+ * returns MTG_INPUT_INFEASIBLE_ROLL_PITCH_RATES: a roll/pitch bound above the limit splits the section until it is
+ * shorter than min_section_time_s, which is MTG_INPUT_INDETERMINABLE.                                            */
+enum {
+  MTG_INPUT_FEASIBLE = 0,
+  MTG_INPUT_INDETERMINABLE = 1,
+  MTG_INPUT_INFEASIBLE_THRUST_HIGH = 2,
+  MTG_INPUT_INFEASIBLE_THRUST_LOW = 3,
+  MTG_INPUT_INFEASIBLE_VELOCITY = 4,
+  MTG_INPUT_INFEASIBLE_ROLL_PITCH_RATES = 5,
+  MTG_INPUT_INFEASIBLE_YAW_RATES = 6,
+  MTG_INPUT_INFEASIBLE_YAW_ACC = 7
+};
+
+/* Per segment, in this order, first hit decides: thrust (minimum below f_min before maximum above f_max), velocity,
+ * yaw rate, yaw acceleration, roll/pitch sections; dimension other than 3 or 4: MTG_INPUT_INDETERMINABLE for every
+ * segment.  Per trajectory: the result of the first segment (in segment order) that is not feasible.
+ *   n_coeffs              5 .. 12 (the jerk polynomial must be at least linear; Polynomial::kMaxN = 12)
+ *   times                 times[b * times_stride_b + k * times_stride_k]; strides >= 1, [B][K] or [K][B] without overlap
+ *   trajectory_result out [batch]; required
+ *   first_failing_segment out optional [batch]: index of that segment, -1 if none
+ *   segment_result    out optional [batch][K]
+ *   segment_bounds    out optional [batch][K][6], 16-byte aligned: thrust minimum, thrust maximum, velocity maximum,
+ *                         roll/pitch bound of the whole segment, |yaw rate| maximum, |yaw acceleration| maximum; NaN
+ *                         where the quantity's limit is absent (not computed)
+ * The real roots of the magnitude derivatives are isolated directly instead of running Jenkins-Traub (as
+ * mtg_minmax_magnitude): same extrema values; a verdict can differ from the reference's only where a bound lies
+ * within rounding of its limit or a candidate's time within rounding of a section's end.
+ * Device pointers; asynchronous on the context's stream.  Argument errors: MTG_ERR_INVALID_ARGUMENT, nothing enqueued. */
+int mtg_check_input_feasibility(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                                const double* coeffs, const double* times, int64_t times_stride_b,
+                                int64_t times_stride_k, const mtg_input_constraints* constraints,
+                                int32_t* trajectory_result, int32_t* first_failing_segment, int32_t* segment_result,
+                                double* segment_bounds);
+/* The same check with HOST pointers on the library's host build of the same code, synchronous; needs no context and
+ * no device (the reference's one-trajectory-at-a-time callers).  segment_bounds needs no alignment here.          */
+int mtg_check_input_feasibility_host(int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                                     const double* coeffs, const double* times, int64_t times_stride_b,
+                                     int64_t times_stride_k, const mtg_input_constraints* constraints,
+                                     int32_t* trajectory_result, int32_t* first_failing_segment,
+                                     int32_t* segment_result, double* segment_bounds);
+
 /* ---- mixed requests: several plans in one launch ------------------------------------------
  * What a caller of the reference does with a list of independent PolynomialOptimization<N>
  * problems of different structure (BASELINE config 4: N in {8, 10, 12}, 4..32 segments): each

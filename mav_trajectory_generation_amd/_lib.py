@@ -33,6 +33,11 @@ class MultiItem(ctypes.Structure):
                 ("cost", ctypes.c_void_p)]
 
 
+class InputConstraintsC(ctypes.Structure):   # mtg_input_constraints: NaN = limit absent
+    _fields_ = [(n, ctypes.c_double) for n in ("f_min", "f_max", "v_max", "omega_xy_max", "omega_z_max", "omega_z_dot_max",
+                                               "min_section_time_s", "gravity")]
+
+
 EXPORTS = {
     "mtg_context_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "mtg_context_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -110,6 +115,15 @@ EXPORTS = {
         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
         ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, c_double_p, c_double_p,
         ctypes.c_void_p]),
+    "mtg_input_constraints_init": (None, [ctypes.POINTER(InputConstraintsC)]),
+    "mtg_input_constraints_set_defaults": (None, [ctypes.POINTER(InputConstraintsC)]),
+    "mtg_check_input_feasibility": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
+        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        c_double_p]),
+    "mtg_check_input_feasibility_host": (ctypes.c_int, [
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
+        ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p]),
     "mtg_multi_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MultiItem), ctypes.c_uint32,
                                         ctypes.POINTER(ctypes.c_void_p)]),
     "mtg_multi_solve": (ctypes.c_int, [ctypes.c_void_p]),

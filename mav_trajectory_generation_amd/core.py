@@ -9,6 +9,7 @@ torch is used only to own device memory and streams.
 from __future__ import annotations
 
 import ctypes
+import enum
 from typing import Optional, Sequence
 
 import numpy as np
@@ -205,6 +206,131 @@ def scale_segment_times_to_meet_constraints(ctx: "Context", coeffs, times, v_max
     ctx._leave(cur)
     _check(ctx.lib, rc, ctx.handle)
     return scaling, within, workspace
+
+
+class InputFeasibilityResult(enum.IntEnum):
+    """The reference's enum InputFeasibilityResult (mav_trajectory_generation_ros feasibility_base.h:34-50)."""
+    kInputFeasible = 0
+    kInputIndeterminable = 1
+    kInputInfeasibleThrustHigh = 2
+    kInputInfeasibleThrustLow = 3
+    kInputInfeasibleVelocity = 4
+    kInputInfeasibleRollPitchRates = 5
+    kInputInfeasibleYawRates = 6
+    kInputInfeasibleYawAcc = 7
+
+
+_RESULT_NAMES = ("Feasible", "Indeterminable", "InfeasibleThrustHigh", "InfeasibleThrustLow", "InfeasibleVelocity",
+                 "InfeasibleRollPitchRates", "InfeasibleYawRates", "InfeasibleYawAcc")
+
+
+def get_input_feasibility_result_name(result: int) -> str:
+    """getInputFeasibilityResultName: the enumerator without its kInput prefix."""
+    result = int(result)
+    return _RESULT_NAMES[result] if 0 <= result < len(_RESULT_NAMES) else "Unknown!"
+
+
+class InputConstraints:
+    """The reference's InputConstraints (input_constraints.h): up to six optional limits, stored by magnitude.  Adding f_min
+    while f_max exists raises f_max to at least it, and the mirror case.  gravity enters the thrust ||a + (0, 0, gravity)||
+    and the default thrust limits; min_section_time_s is FeasibilityAnalytic::Settings' (stored by magnitude too)."""
+    NAMES = ("f_min", "f_max", "v_max", "omega_xy_max", "omega_z_max", "omega_z_dot_max")
+    GRAVITY = 9.81   # mav_msgs::kGravity upstream
+
+    def __init__(self, min_section_time_s: float = 0.05, gravity: float = GRAVITY, **limits):
+        self.constraints = {}
+        self.min_section_time_s = abs(float(min_section_time_s))
+        self.gravity = float(gravity)
+        for name, value in limits.items():
+            self.add_constraint(name, value)
+
+    @classmethod
+    def defaults(cls, **kw) -> "InputConstraints":
+        c = cls(**kw)
+        c.set_default_values()
+        return c
+
+    def add_constraint(self, name: str, value: float):
+        if name not in self.NAMES:
+            raise KeyError(name)
+        value = abs(float(value))
+        if name == "f_min" and "f_max" in self.constraints:
+            self.constraints["f_max"] = max(value, self.constraints["f_max"])
+        elif name == "f_max" and "f_min" in self.constraints:
+            self.constraints["f_min"] = min(value, self.constraints["f_min"])
+        self.constraints[name] = value
+
+    def set_default_values(self):
+        import math
+        self.constraints.update(f_min=0.5 * self.gravity, f_max=1.5 * self.gravity, v_max=3.0, omega_xy_max=math.pi / 2.0,
+                                omega_z_max=math.pi / 2.0, omega_z_dot_max=2.0 * math.pi)
+
+    def has_constraint(self, name: str) -> bool:
+        return name in self.constraints
+
+    def get_constraint(self, name: str) -> Optional[float]:
+        return self.constraints.get(name)
+
+    def remove_constraint(self, name: str) -> bool:
+        return self.constraints.pop(name, None) is not None
+
+    def to_c(self) -> L.InputConstraintsC:
+        c = L.InputConstraintsC(*[self.constraints.get(n, float("nan")) for n in self.NAMES], self.min_section_time_s, self.gravity)
+        return c
+
+
+def check_input_feasibility(ctx: "Context", coeffs, times, constraints: InputConstraints, times_layout: str = "aos",
+                            want_segments: bool = True, want_bounds: bool = True):
+    """Batched FeasibilityAnalytic::checkInputFeasibilityTrajectory: coeffs [B][K][D][N], times ([B][K] 'aos' / [K][B] 'soa')
+    CUDA tensors -> (trajectory_result [B] int32, first_failing_segment [B] int32 (-1: none), segment_result [B][K] int32 or
+    None, segment_bounds [B][K][6] or None: thrust min, thrust max, velocity max, whole-segment roll/pitch bound, |yaw rate|
+    max, |yaw acceleration| max; NaN where not computed).  Result codes: InputFeasibilityResult."""
+    import torch
+    bsz, k, dim, n = coeffs.shape
+    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
+    dev = coeffs.device
+    traj = torch.empty((bsz,), dtype=torch.int32, device=dev)
+    first = torch.empty((bsz,), dtype=torch.int32, device=dev)
+    seg = torch.empty((bsz, k), dtype=torch.int32, device=dev) if want_segments else None
+    bounds = torch.empty((bsz, k, 6), dtype=torch.float64, device=dev) if want_bounds else None
+    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
+    c = constraints.to_c()
+    cur = ctx._enter()
+    rc = ctx.lib.mtg_check_input_feasibility(ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()),
+                                             ctypes.c_void_p(times.data_ptr()), sb, sk, ctypes.byref(c),
+                                             ctypes.c_void_p(traj.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+                                             ctypes.c_void_p(seg.data_ptr()) if seg is not None else None,
+                                             ctypes.c_void_p(bounds.data_ptr()) if bounds is not None else None)
+    ctx._leave(cur)
+    _check(ctx.lib, rc, ctx.handle)
+    return traj, first, seg, bounds
+
+
+def check_input_feasibility_host(coeffs, times, constraints: InputConstraints, times_layout: str = "aos"):
+    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
+    [B][K][D][N] or one trajectory [K][D][N]; returns numpy (trajectory_result, first_failing_segment, segment_result,
+    segment_bounds), shaped as the device form's (without the batch axis for one trajectory)."""
+    lib = L.load()
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    single = coeffs.ndim == 3
+    if single:
+        coeffs, times = coeffs[None], times[None]
+    bsz, k, dim, n = coeffs.shape
+    if times.size != bsz * k:
+        raise MtgError(-1, "times must hold one value per segment")
+    traj = np.empty((bsz,), dtype=np.int32)
+    first = np.empty((bsz,), dtype=np.int32)
+    seg = np.empty((bsz, k), dtype=np.int32)
+    bounds = np.empty((bsz, k, 6), dtype=np.float64)
+    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
+    c = constraints.to_c()
+    rc = lib.mtg_check_input_feasibility_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk, ctypes.byref(c),
+                                              traj.ctypes.data, first.ctypes.data, seg.ctypes.data, bounds.ctypes.data)
+    _check(lib, rc)
+    if single:
+        return traj[0], first[0], seg[0], bounds[0]
+    return traj, first, seg, bounds
 
 
 class Plan:

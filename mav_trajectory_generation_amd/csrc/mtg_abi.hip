@@ -370,6 +370,9 @@ int mtg_context_stream_device(mtg_context* ctx, void** stream, int* device) {
   return MTG_OK;
 }
 
+// ... and the context's error text (mtg_feasibility.hip: argument errors say which argument)
+int mtg_context_set_last_error(mtg_context* ctx, int code, const char* message) { return set_err(ctx, code, message ? message : ""); }
+
 // ---- device memory helpers: host code above the C ABI never sees HIP headers ---------------------------------
 int mtg_device_malloc(mtg_context* ctx, size_t bytes, void** device_ptr) {
   if (!ctx || !device_ptr) return MTG_ERR_INVALID_ARGUMENT;
