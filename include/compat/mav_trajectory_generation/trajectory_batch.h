@@ -2,11 +2,13 @@
 // batched forms of the reference's post-solve Trajectory functions running on the MI355X through the C ABI
 // (include/mtg_hip.h): evaluateRange / sampleTrajectoryInRange -> sample(), computeMinMaxMagnitude,
 // computeMaxVelocityAndAcceleration, scaleSegmentTimesToMeetConstraints (src/trajectory.cpp:81-141, :190-227,
-// :343-361, :385-429).  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
+// :343-361, :385-429), and softConstraintCost -- the soft-constraint term of the time optimisers' objective
+// (PolynomialOptimizationNonLinear<N>::evaluateMaximumMagnitudeAsSoftConstraint).  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
 // The single-trajectory functions stay on the host (trajectory.h); this class is for B >> 1.
 #ifndef MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
 #define MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "../../mtg_hip.h"
@@ -76,6 +78,39 @@ class TrajectoryBatch {
     a_max->resize(B_);
     for (int64_t b = 0; b < B_ && ok; ++b) (*a_max)[b] = mx[b].value;
     return ok;
+  }
+
+  // The soft-constraint cost of every trajectory (the third term of PolynomialOptimizationNonLinear<N>::
+  // getTotalCostWithSoftConstraints): sum over `constraints` = (derivative, maximum allowed magnitude) pairs, in their order, of
+  // min(maximum_cost, exp(weight * (max ||p^(derivative)|| / value - 1))).  maxima (optional): [size()][constraints.size()].
+  // false: more than MTG_MAX_MAGNITUDE_CONSTRAINTS constraints, a derivative outside 1 .. N/2 - 1, a value <= 0 or D > 4.
+  bool softConstraintCost(const std::vector<std::pair<int, double>>& constraints, double weight, std::vector<double>* cost,
+                          std::vector<double>* maxima = nullptr, double maximum_cost = 1.0e12) {
+    CHECK_NOTNULL(cost);
+    if (constraints.size() > MTG_MAX_MAGNITUDE_CONSTRAINTS || D_ > 4) return false;
+    mtg_time_objective_params params;
+    mtg_time_objective_params_init(&params);
+    params.soft_constraint_weight = weight;
+    params.maximum_cost = maximum_cost;
+    params.n_constraints = (int32_t)constraints.size();
+    for (size_t q = 0; q < constraints.size(); ++q) {
+      if (constraints[q].first < 1 || constraints[q].first > N_ / 2 - 1 || !(constraints[q].second > 0.0)) return false;
+      params.derivative[q] = constraints[q].first;
+      params.value[q] = constraints[q].second;
+    }
+    const size_t n = constraints.size();
+    double* d_cost = (double*)dmalloc(sizeof(double) * B_);
+    double* d_max = n ? (double*)dmalloc(sizeof(double) * B_ * n) : nullptr;
+    check(mtg_magnitude_soft_cost(ctx(), N_, K_, D_, B_, coeffs_, times_, K_, 1, &params, d_cost, d_max, nullptr));
+    cost->resize(B_);
+    check(mtg_copy_to_host(ctx(), cost->data(), d_cost, sizeof(double) * B_));
+    if (maxima) {
+      maxima->resize(B_ * n);
+      if (n) check(mtg_copy_to_host(ctx(), maxima->data(), d_max, sizeof(double) * B_ * n));
+    }
+    mtg_device_free(ctx(), d_cost);
+    if (d_max) mtg_device_free(ctx(), d_max);
+    return true;
   }
 
   // In place on the device copy; returns true when every trajectory ended within range.

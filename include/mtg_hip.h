@@ -407,6 +407,74 @@ int mtg_check_input_feasibility_host(int32_t n_coeffs, int32_t n_segments, int32
                                      int32_t* trajectory_result, int32_t* first_failing_segment,
                                      int32_t* segment_result, double* segment_bounds);
 
+/* ---- the time optimisers' objective with soft constraints ---------------------------------------
+ * Replaces, for a batch, the callbacks PolynomialOptimizationNonLinear<N> hands to nlopt
+ * (impl/polynomial_optimization_nonlinear_impl.h, NL below): objectiveFunctionTime (NL:556-615) and
+ * objectiveFunctionTimeAndConstraints (NL:660-742) = cost_trajectory + cost_time + cost_soft, with
+ *   cost_trajectory = computeCost() after updateSegmentTimes + solveLinear (or + setFreeConstraints),
+ *   cost_time       = time_penalty * T^2 (the squared-time kinds) or time_penalty * T (the Richter kinds), T = sum of the
+ *                     segment times in segment order,
+ *   cost_soft       = sum over the constraints, in their order, of
+ *                     min(maximum_cost, exp(soft_constraint_weight * (max ||p^(derivative)|| / value - 1)))
+ *                     (evaluateMaximumMagnitudeAsSoftConstraint NL:767-795 over computeMaximumOfMagnitude LIN:466-497).
+ * Accepted derivatives: 1 .. N/2 - 1 -- continuous across vertices, so that the reference's candidate set (segment starts,
+ * interior critical points, the end of the last segment) holds the true maximum; its own N - derivative - 1 > 0 check is
+ * implied.  Values must be > 0.  dimension <= 4 (a lane keeps a segment's D x N coefficients in registers).             */
+#define MTG_MAX_MAGNITUDE_CONSTRAINTS 4
+enum { /* NonlinearOptimizationParameters::TimeAllocMethod */
+  MTG_TIME_SQUARED = 0,
+  MTG_TIME_RICHTER = 1,
+  MTG_TIME_MELLINGER_OUTER_LOOP = 2, /* (no time or soft term upstream: not accepted here) */
+  MTG_TIME_SQUARED_AND_CONSTRAINTS = 3,
+  MTG_TIME_RICHTER_AND_CONSTRAINTS = 4
+};
+typedef struct mtg_time_objective_params {
+  int32_t time_cost_kind;         /* MTG_TIME_*; decides T^2 against T only                                          */
+  int32_t use_soft_constraints;   /* 0: cost_soft = 0 (maxima are still written when asked for)                      */
+  double time_penalty;            /* 500                                                                             */
+  double soft_constraint_weight;  /* 100                                                                             */
+  double maximum_cost;            /* 1e12: cap of each soft term                                                     */
+  int32_t n_constraints;          /* 0 .. MTG_MAX_MAGNITUDE_CONSTRAINTS, in the order of addMaximumMagnitudeConstraint */
+  int32_t derivative[MTG_MAX_MAGNITUDE_CONSTRAINTS];
+  double value[MTG_MAX_MAGNITUDE_CONSTRAINTS];
+} mtg_time_objective_params;
+/* NonlinearOptimizationParameters' defaults (kSquaredTimeAndConstraints, 500, soft constraints on, 100, 1e12), no constraints */
+void mtg_time_objective_params_init(mtg_time_objective_params* params);
+
+/* d_free_in == NULL: objectiveFunctionTime -- the plan's ordinary solve (coefficients + cost) into `coeffs`;
+ * d_free_in != NULL: objectiveFunctionTimeAndConstraints -- mtg_update_segments_from_free on the caller's free constraints.
+ * Then ONE search launch (a lane per (trajectory, segment) reads its coefficients once and searches every constrained
+ * derivative, maxima only) and a lane per trajectory that forms the components.
+ *   coeffs     out [batch][K][D][N], 16-byte aligned; required
+ *   objective  out [batch]; required.  +inf for a trajectory the solve flags (segment time <= 0, breakdown); the context's
+ *                  flag is raised as for any solve (mtg_context_sync)
+ *   components out optional [batch][3] = (cost_trajectory, cost_time, cost_soft)
+ *   maxima     out optional [batch][n_constraints]
+ *   violations out optional [batch][n_constraints] = maximum - value (evaluateMaximumMagnitudeConstraint NL:745-763)
+ * Device pointers; asynchronous on the context's stream.  The plan keeps 48 bytes of workspace per trajectory, grown by
+ * the first call of a batch size (like mtg_mellinger_cost_gradient's): capture a call after one plain call of that size.
+ * Argument errors: MTG_ERR_INVALID_ARGUMENT, nothing enqueued.                                                          */
+int mtg_time_objective(mtg_plan* plan, int64_t batch, const mtg_layout* layout, const double* times, const double* d_fixed,
+                       const double* d_free_in, const mtg_time_objective_params* params, double* coeffs, double* objective,
+                       double* components, double* maxima, double* violations);
+/* The maxima + soft-cost stage alone on existing coefficients [batch][K][D][N] (getTotalCostWithSoftConstraints' third term):
+ *   cost_soft out [batch]; required.  maxima required too here ([batch][n_constraints]: the search reduces into it);
+ *   violations optional.  times[b * times_stride_b + k * times_stride_k] as in mtg_minmax_magnitude.                     */
+int mtg_magnitude_soft_cost(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                            const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                            const mtg_time_objective_params* params, double* cost_soft, double* maxima, double* violations);
+/* The same with HOST pointers on the library's host build of the same lane code, synchronous; needs no context and no device.
+ * maxima is optional here.                                                                                              */
+int mtg_magnitude_soft_cost_host(int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch, const double* coeffs,
+                                 const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                                 const mtg_time_objective_params* params, double* cost_soft, double* maxima,
+                                 double* violations);
+
+/* cost_time alone, on the host: cost_time[b] = time_penalty * T^2 or * T (by params->time_cost_kind), T = the sum of
+ * times[b * times_stride_b + k * times_stride_k] in segment order -- the expression the device entry evaluates.         */
+int mtg_time_cost_host(const mtg_time_objective_params* params, int32_t n_segments, int64_t batch, const double* times,
+                       int64_t times_stride_b, int64_t times_stride_k, double* cost_time);
+
 /* ---- mixed requests: several plans in one launch ------------------------------------------
  * What a caller of the reference does with a list of independent PolynomialOptimization<N>
  * problems of different structure (BASELINE config 4: N in {8, 10, 12}, 4..32 segments): each

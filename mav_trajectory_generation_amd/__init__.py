@@ -11,3 +11,6 @@ from .core import get_input_feasibility_result_name  # noqa: F401
 from .workload import ends_full_masks, random_waypoint_batch  # noqa: F401
 from .buckets import MergedRequest, MixedBatchSolver  # noqa: F401
 from .time_gradient import mellinger_cost_and_gradient  # noqa: F401
+from .time_objective_search import TimeObjectiveParams, TimeObjectiveResult, TimeCostKind, time_objective  # noqa: F401
+from .time_objective_search import magnitude_soft_cost, magnitude_soft_cost_host, pattern_search_segment_times  # noqa: F401
+from .time_objective_search import PatternSearchResult, time_cost_host  # noqa: F401

@@ -38,6 +38,12 @@ class InputConstraintsC(ctypes.Structure):   # mtg_input_constraints: NaN = limi
                                                "min_section_time_s", "gravity")]
 
 
+class TimeObjectiveParamsC(ctypes.Structure):   # mtg_time_objective_params
+    _fields_ = [("time_cost_kind", ctypes.c_int32), ("use_soft_constraints", ctypes.c_int32), ("time_penalty", ctypes.c_double),
+                ("soft_constraint_weight", ctypes.c_double), ("maximum_cost", ctypes.c_double), ("n_constraints", ctypes.c_int32),
+                ("derivative", ctypes.c_int32 * 4), ("value", ctypes.c_double * 4)]
+
+
 EXPORTS = {
     "mtg_context_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "mtg_context_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -124,6 +130,18 @@ EXPORTS = {
     "mtg_check_input_feasibility_host": (ctypes.c_int, [
         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
         ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p]),
+    "mtg_time_objective_params_init": (None, [ctypes.POINTER(TimeObjectiveParamsC)]),
+    "mtg_time_objective": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Layout), c_double_p, c_double_p, c_double_p,
+                                          ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p, c_double_p,
+                                          c_double_p]),
+    "mtg_magnitude_soft_cost": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64,
+        ctypes.c_int64, ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p]),
+    "mtg_magnitude_soft_cost_host": (ctypes.c_int, [
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
+        ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p]),
+    "mtg_time_cost_host": (ctypes.c_int, [ctypes.POINTER(TimeObjectiveParamsC), ctypes.c_int32, ctypes.c_int64, c_double_p,
+                                          ctypes.c_int64, ctypes.c_int64, c_double_p]),
     "mtg_multi_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MultiItem), ctypes.c_uint32,
                                         ctypes.POINTER(ctypes.c_void_p)]),
     "mtg_multi_solve": (ctypes.c_int, [ctypes.c_void_p]),

@@ -188,6 +188,8 @@ struct mtg_plan {
   size_t ws_bytes = 0;
   double* pert_cost = nullptr;      // [(K + 1)][batch] costs of mtg_mellinger_cost_gradient's virtual problems
   size_t pert_cost_bytes = 0;
+  double* objective_ws = nullptr;   // mtg_time_objective: cost [batch] | maxima slots [batch][4] | per-trajectory status int32 [batch]
+  size_t objective_ws_bytes = 0;
   double* user_ws = nullptr;       // caller-owned workspace (mtg_plan_set_workspace)
   size_t user_ws_bytes = 0;
   // staging for MTG_FLAG_HOST_POINTERS
@@ -679,6 +681,7 @@ int mtg_plan_destroy(mtg_plan* p) {
   if (p->d_tables) hipFree(p->d_tables);
   if (p->ws) hipFree(p->ws);
   if (p->pert_cost) hipFree(p->pert_cost);
+  if (p->objective_ws) hipFree(p->objective_ws);
   if (p->stage) hipFree(p->stage);
   if (p->basic_status) hipFree(p->basic_status);
   if (p->d_shadow_maps) hipFree(p->d_shadow_maps);
@@ -1736,6 +1739,26 @@ int mtg_update_segments_from_free(mtg_plan* plan, int64_t batch, const mtg_layou
                                   const double* d_fixed, const double* d_free, double* coeffs, double* cost,
                                   uint32_t flags) {
   return solve_impl(plan, batch, layout, times, d_fixed, coeffs, const_cast<double*>(d_free), cost, flags, true);
+}
+
+// used by mtg_objective.hip: the solve stage of mtg_time_objective -- the plan's ordinary launch forms (coefficients + cost; with
+// d_free_in the update-from-free path) into the caller's coefficient buffer, cost and per-trajectory status into the plan's
+// workspace, whose three parts are returned
+int mtg_plan_objective_solve(mtg_plan* plan, int64_t batch, const mtg_layout* layout, const double* times, const double* d_fixed,
+                             const double* d_free_in, double* coeffs, double** cost, double** slots, int32_t** tstatus) {
+  if (!plan || !cost || !slots || !tstatus || batch <= 0) return MTG_ERR_INVALID_ARGUMENT;
+  mtg_context* ctx = plan->ctx;
+  {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    MTG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = ensure_buffer(ctx, &plan->objective_ws, &plan->objective_ws_bytes, (size_t)batch * 48);
+    if (rc != MTG_OK) return rc;
+  }
+  *cost = plan->objective_ws;
+  *slots = plan->objective_ws + batch;
+  *tstatus = reinterpret_cast<int32_t*>(plan->objective_ws + 5 * batch);
+  return solve_impl(plan, batch, layout, times, d_fixed, coeffs, const_cast<double*>(d_free_in), *cost, 0, d_free_in != nullptr,
+                    *tstatus);
 }
 
 // ---- mixed requests ---------------------------------------------------------------------------

@@ -1,0 +1,39 @@
+"""TrajectoryBatch::softConstraintCost of the C++ compat veneer (include/compat/mav_trajectory_generation/trajectory_batch.h) over
+mtg_magnitude_soft_cost, next to the library's host entry, against rows of the reference's own maxima and soft cost.  The program
+is built with plain g++ against the C ABI."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "tests", "cpp", "test_objective_veneer")
+ROWS = os.path.join(ROOT, "tests", "golden", "reference_time_objective_veneer_rows.txt")
+
+
+def build_exe():
+    src = os.path.join(ROOT, "tests", "cpp", "test_objective_veneer.cpp")
+    d = os.path.join(ROOT, "include", "compat", "mav_trajectory_generation")
+    deps = [src, os.path.join(ROOT, "include", "mtg_hip.h")] + [os.path.join(d, f) for f in os.listdir(d)]
+    if os.path.exists(EXE) and all(os.path.getmtime(EXE) >= os.path.getmtime(p) for p in deps):
+        return
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I" + os.path.join(ROOT, "include", "compat"), "-I" + os.path.join(ROOT, "include"),
+                           "-o", EXE, src, "-L" + os.path.join(ROOT, "mav_trajectory_generation_amd", "csrc"), "-lmtg_hip", "-pthread",
+                           "-Wl,-rpath,$ORIGIN/../../mav_trajectory_generation_amd/csrc"])
+
+
+def test_objective_veneer_on_the_host():
+    build_exe()
+    undefined = subprocess.run(["nm", "-D", "--undefined-only", EXE], capture_output=True, text=True).stdout
+    assert "mtg_magnitude_soft_cost_host" in undefined and "mtg_magnitude_soft_cost\n" in undefined
+    r = subprocess.run([EXE, ROWS, "host"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "OBJECTIVE VENEER TESTS PASSED (host)" in r.stdout
+
+
+@pytest.mark.gpu
+def test_objective_veneer_on_the_device():
+    build_exe()
+    r = subprocess.run([EXE, ROWS, "device"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "OBJECTIVE VENEER TESTS PASSED (host + device)" in r.stdout
