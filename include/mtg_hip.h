@@ -305,7 +305,15 @@ int mtg_mellinger_cost_gradient(mtg_plan* plan, int64_t batch, const mtg_layout*
  *   out[b][i][der][dim] = der-th derivative of dimension dim at t_i = t_start + i*dt,  i < n_samples,
  * der < n_derivatives (5 = position .. snap), from coeffs[batch][K][D][N] and times[b*stride_b + k*stride_k].
  * Samples beyond a trajectory's end are evaluated at its end; n_valid[b] (optional) = number of samples with
- * t_i <= total time.  Device pointers (out 16-byte aligned); asynchronous on the context's stream.          */
+ * t_i <= total time.  Device pointers (out 16-byte aligned); asynchronous on the context's stream.
+ * Rounding, so that a host caller can reproduce every choice the kernels make:
+ *   t_i        the float64 value fl(t_start + fl(i * dt)): TWO roundings, never one fused multiply-add -- what a host loop that
+ *              builds the timestamps as `t_start + i * dt` obtains; the sampler and n_valid use the same value;
+ *   segment    the first k whose float64 prefix sum  acc_k = fl(acc_{k-1} + times[k])  (acc_{-1} = 0, sequential) exceeds t_i
+ *              (a sample exactly on a vertex belongs to the segment on its right; none: the last segment);
+ *   seg_start  acc_{k-1}: the prefix sum BEFORE the segment's own time is added (not acc_k - times[k]);
+ *   local      min(fl(t_i - seg_start), times[k]); t_i < 0 extrapolates segment 0 with a negative local time;
+ *   total time acc_{K-1}.                                                                                      */
 int mtg_sample_range(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
                      const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
                      double t_start, double dt, int32_t n_samples, int32_t n_derivatives, double* out,

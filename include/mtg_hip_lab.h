@@ -22,6 +22,8 @@
  *   "extrema_split"    -1 default; bits 0-1: lanes that share one root search of the extrema kernels (1, 2, 3 = four; 0 = by
  *                      launch size, the default); bit 2: one code body for all levels of the derivative chain
  *   "sample_generic"   0 / 1                       mtg_sample_range never through its compile-time-shape kernels
+ *   "sample_max_blocks" 0 default, >= 1            upper limit of the persistent grid (workgroups) of mtg_sample_range: a small launch
+ *                      then runs every wave through several steps of its pipeline (tests/test_gpu_sampling.py)
  * Returns MTG_OK, or MTG_ERR_INVALID_ARGUMENT for an unknown name.                                                  */
 #ifndef MTG_HIP_LAB_H_
 #define MTG_HIP_LAB_H_

@@ -137,14 +137,35 @@ class Context:
 
 
 def sample_range(ctx: "Context", coeffs, times, t_start: float, dt: float, n_samples: int, n_derivatives: int = 5,
-                 times_layout: str = "aos", want_valid: bool = False):
+                 times_layout: str = "aos", want_valid: bool = False, out=None, valid=None):
     """Batched Trajectory::evaluateRange / sampleTrajectoryInRange: coeffs [B][K][D][N] and times ([B][K] 'aos' or
-    [K][B] 'soa') CUDA tensors -> out [B][n_samples][n_derivatives][D] (and n_valid [B] int32)."""
+    [K][B] 'soa') CUDA tensors -> out [B][n_samples][n_derivatives][D] (and n_valid [B] int32).
+    `out` / `valid`: caller-owned result buffers (float64 / int32 CUDA tensors of exactly that many elements on the device of
+    `coeffs`, contiguous, `out` 16-byte aligned) instead of fresh allocations; `valid` implies want_valid.  The results are
+    views of them in the shapes above."""
     import torch
     bsz, k, dim, n = coeffs.shape
     assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
-    out = torch.empty((bsz, n_samples, n_derivatives, dim), dtype=torch.float64, device=coeffs.device)
-    valid = torch.empty((bsz,), dtype=torch.int32, device=coeffs.device) if want_valid else None
+    shape = (bsz, n_samples, n_derivatives, dim)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=coeffs.device)
+    else:
+        if not (out.is_cuda and out.device == coeffs.device and out.dtype == torch.float64):
+            raise ValueError("sample_range: `out` must be a float64 tensor on the device of `coeffs`")
+        if out.numel() != bsz * n_samples * n_derivatives * dim or not out.is_contiguous():
+            raise ValueError("sample_range: `out` must be contiguous with %d x %d x %d x %d elements" % shape)
+        if out.data_ptr() % 16:
+            raise ValueError("sample_range: `out` must be 16-byte aligned")
+        out = out.view(shape)
+    if valid is None:
+        valid = torch.empty((bsz,), dtype=torch.int32, device=coeffs.device) if want_valid else None
+    else:
+        if not (valid.is_cuda and valid.device == coeffs.device and valid.dtype == torch.int32):
+            raise ValueError("sample_range: `valid` must be an int32 tensor on the device of `coeffs`")
+        if valid.numel() != bsz or not valid.is_contiguous():
+            raise ValueError("sample_range: `valid` must be contiguous with %d elements" % bsz)
+        valid = valid.view((bsz,))
+        want_valid = True
     sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
     cur = ctx._enter()
     rc = ctx.lib.mtg_sample_range(ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()),

@@ -129,6 +129,7 @@ struct mtg_context {
   int knob_slab_policy = -1;         // MTG_SLAB_POLICY: 0 write-back, 1 nt sc1
   int rolled_wg_per_cu = 4;          // MTG_ROLLED_WG_PER_CU: persistent workgroups per CU of the rolled (workspace) kernels
   bool knob_sample_generic = false;  // MTG_SAMPLE_GENERIC: mtg_sample_range never through its LDS-staged kernel
+  int knob_sample_max_blocks = 0;    // MTG_SAMPLE_MAX_BLOCKS: >= 1 caps the persistent grid of mtg_sample_range (0: occupancy x CUs, the shipped grid)
   int knob_extrema_split = -1;       // MTG_EXTREMA_SPLIT: lanes per root search of the extrema kernels (include/mtg_hip_lab.h; -1: default)
   int knob_coop = -1;                // MTG_COOP: 1 always / 0 never take the row-cooperative form where eligible (default: by size)
   // MTG_FLAG_CONCURRENT_ITEMS requests: side streams (created on first use) + fork / join events
@@ -327,6 +328,7 @@ int mtg_context_set_option(mtg_context* ctx, const char* name, int value) {
   else if (n == "rolled_wg_per_cu") ctx->rolled_wg_per_cu = std::max(1, value);
   else if (n == "dl_max_units") ctx->dl_max_units_per_cu = value;
   else if (n == "sample_generic") ctx->knob_sample_generic = value != 0;
+  else if (n == "sample_max_blocks") ctx->knob_sample_max_blocks = std::max(0, value);
   else if (n == "coop") ctx->knob_coop = value;
   else if (n == "extrema_split") ctx->knob_extrema_split = value;
   else return set_err(ctx, MTG_ERR_INVALID_ARGUMENT, "unknown option: " + n);
@@ -335,6 +337,7 @@ int mtg_context_set_option(mtg_context* ctx, const char* name, int value) {
 
 // (mtg_sample.hip, mtg_extrema.hip)
 bool mtg_context_sample_generic(const mtg_context* ctx) { return ctx && ctx->knob_sample_generic; }
+int mtg_context_sample_max_blocks(const mtg_context* ctx) { return ctx ? ctx->knob_sample_max_blocks : 0; }
 int mtg_context_extrema_split(const mtg_context* ctx) { return ctx ? ctx->knob_extrema_split : -1; }
 
 int mtg_context_destroy(mtg_context* ctx) {

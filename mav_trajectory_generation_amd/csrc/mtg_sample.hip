@@ -41,11 +41,21 @@ struct SampleSite {
   double local;      // time inside the segment, clamped to the segment's duration
 };
 
+// Sample time t_i = fl(t_start + fl(i * dt)): TWO roundings, as include/mtg_hip.h defines it (what a host caller who builds the
+// timestamps obtains).  hipcc contracts `a + b * c` into one fma by default; one ulp of difference flips the `acc > t` segment
+// choice of a sample on a vertex and the `t_i <= total` count of n_valid, so the sampler, the pipelined scan and the n_valid
+// kernel all take t_i from here.
+__device__ __forceinline__ double mtg_sample_time(const SampleParams& P, int i) {
+#pragma clang fp contract(off)
+  const double step = P.dt * (double)i;
+  return P.t_start + step;
+}
+
 // (trajectory, sample) -> segment lookup: the first segment whose accumulated end time exceeds t
 // (src/trajectory.cpp:52-66); t at or beyond the last vertex -> last segment, clamped to its end.
 // Branch-free scan (no early exit: the loads of all K times are independent and stay in flight together).
 __device__ __forceinline__ SampleSite mtg_sample_site(const SampleParams& P, long long b, int s) {
-  const double t = P.t_start + P.dt * s;
+  const double t = mtg_sample_time(P, s);
   const double* tt = P.times + b * P.ts_b;
   double acc = 0.0, seg_start = 0.0, seg_time = 0.0;
   int seg = 0;
@@ -232,7 +242,7 @@ __global__ __launch_bounds__(kThreads, KMAX <= 8 ? MTG_SAMPLE_CT_WAVES : 3) void
     for (int i = 0; i < KMAX; ++i) T[i] = tt[(long long)(i < K ? i : K - 1) * P.ts_k];   // branch-free: K <= KMAX
   };
   auto scan = [&](const double (&T)[KMAX], long long b, int s_idx) {
-    const double t = P.t_start + P.dt * s_idx;
+    const double t = mtg_sample_time(P, s_idx);
     double acc = 0.0, seg_start = 0.0, seg_time = T[0];
     int seg = 0;
     bool found = false;
@@ -367,8 +377,8 @@ __global__ void mtg_sample_valid_kernel(SampleParams P) {
   if (total_time >= P.t_start) {
     const double q = (total_time - P.t_start) / P.dt;
     nv = q >= (double)(P.S - 1) ? P.S : (int)q + 1;
-    while (nv < P.S && P.t_start + P.dt * nv <= total_time) ++nv;
-    while (nv > 0 && P.t_start + P.dt * (nv - 1) > total_time) --nv;
+    while (nv < P.S && mtg_sample_time(P, nv) <= total_time) ++nv;
+    while (nv > 0 && mtg_sample_time(P, nv - 1) > total_time) --nv;
   }
   P.n_valid[b] = nv;
 }
@@ -378,6 +388,7 @@ __global__ void mtg_sample_valid_kernel(SampleParams P) {
 // C ABI (declared in include/mtg_hip.h).  The context type is opaque here: only its stream / device are needed.
 extern "C" int mtg_context_stream_device(mtg_context* ctx, void** stream, int* device);
 extern "C" bool mtg_context_sample_generic(const mtg_context* ctx);   // measurement knob "sample_generic" (mtg_hip_lab.h)
+extern "C" int mtg_context_sample_max_blocks(const mtg_context* ctx);  // measurement knob "sample_max_blocks" (mtg_hip_lab.h)
 
 extern "C" int mtg_sample_range(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
                                 const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
@@ -429,6 +440,8 @@ extern "C" int mtg_sample_range(mtg_context* ctx, int32_t n_coeffs, int32_t n_se
     per_cu = 4;
   if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) n_cu = 256;
   if (blocks > (long long)per_cu * n_cu) blocks = (long long)per_cu * n_cu;
+  const int max_blocks = mtg_context_sample_max_blocks(ctx);   // 0 (shipped): no further cap; tests run every worker through several sweeps
+  if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
   hipLaunchKernelGGL(launch_fn, dim3((unsigned)blocks), dim3(kThreads), launch_lds, (hipStream_t)stream, P, total);
   if (n_valid)
     hipLaunchKernelGGL(mtg_sample_valid_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P);
