@@ -399,7 +399,7 @@ MTG_HD void mtg_load_vals(const MtgParams& P, long long b, int v, int mask, cons
 // The pivot test `!(d > 0)` is a BREAKDOWN guard (the matrix is numerically not positive definite: NaN inputs, problems beyond
 // float64 such as N = 12 chains with segment-time ratios of 400), not the rank decision.  Whether the free system is
 // rank-deficient -- where the reference's rank-revealing SparseQR returns a basic solution, LIN:365-378 -- is a property of
-// the constraint PATTERN and is decided once per plan on the host (mtg_abi.hip: structural_null_dim; every trajectory of such
+// the constraint PATTERN and is decided once per plan on the host (mtg_plan.hip: structural_null_dim; every trajectory of such
 // a plan is flagged, and MTG_FLAG_BASIC_SOLUTION solves it through the plan's pinned shadow).  Round 5 built and measured the
 // alternative the round-4 review asked for, a relative threshold d_j <= 20 (n_free + n_free) eps R_PP[j][j] (SparseQR's default
 // form, the diagonal carried through the chain: +2 % on small launches), and took it out again: on chains of free vertices

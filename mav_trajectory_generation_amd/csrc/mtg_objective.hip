@@ -138,7 +138,7 @@ extern "C" int mtg_context_stream_device(mtg_context* ctx, void** stream, int* d
 extern "C" int mtg_context_set_last_error(mtg_context* ctx, int code, const char* message);   // mtg_abi.hip
 extern "C" int mtg_plan_objective_solve(mtg_plan* plan, int64_t batch, const mtg_layout* layout, const double* times,
                                         const double* d_fixed, const double* d_free_in, double* coeffs, double** cost, double** slots,
-                                        int32_t** tstatus);   // mtg_abi.hip
+                                        int32_t** tstatus);   // mtg_dispatch.hip
 extern "C" int mtg_objective_constraints(const mtg_time_objective_params* in, mtgo::Constraints* out);   // mtg_objective_host.cpp
 
 extern "C" int mtg_time_objective(mtg_plan* plan, int64_t batch, const mtg_layout* layout, const double* times,

@@ -11,7 +11,7 @@
 // and the sums over a segment's twelve columns and over a vertex's two segments accumulated in double-double (two-sum / two-prod
 // with FMA).  One such step takes the worst of 400 N = 12 / K = 16 trajectories from 2e-7 to 5e-15 (profiles/r06_n12_refinement.txt):
 // the float64 factorisation is an excellent preconditioner (cond x eps ~ 2e-7 is the contraction per step).
-// The correction solve R_PP delta = r and the coefficient recovery are the ordinary float64 kernels (mtg_abi.hip: solve_refined).
+// The correction solve R_PP delta = r and the coefficient recovery are the ordinary float64 kernels (mtg_shadow.hip: solve_refined).
 //
 // One thread per (trajectory, dimension); walks the segments once, keeps the double-double partial sums of the vertex it shares
 // with the next segment.  Generic over masks / strides (it reads the plan's device tables): this is an accuracy mode, not the

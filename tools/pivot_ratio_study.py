@@ -1,4 +1,4 @@
-"""Evidence behind the structural rank decision (tests/test_pivot_threshold.py, csrc/mtg_abi.hip structural_null_dim): how large
+"""Evidence behind the structural rank decision (tests/test_pivot_threshold.py, csrc/mtg_plan.hip structural_null_dim): how large
 does the pivot that is ZERO in exact arithmetic come out of a float64 LDL^T of R_PP (the reference's own R = M^T H M,
 LIN:308-336, from oracle/_ref), relative to the variable's own diagonal entry and to the largest one -- against the smallest
 legitimate pivot of regular ill-conditioned problems.  Test infrastructure (imports oracle/); output committed as
