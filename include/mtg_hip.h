@@ -201,7 +201,8 @@ int mtg_structural_rank_deficiency(int32_t n_coeffs, int32_t n_segments, int32_t
  * (with MTG_FLAG_QUERY_EXTRA_OUTPUTS: a call that also returns the cost / d_free) takes on this device: 0 generic (run-time K / masks), 1 fused static, 2 dimension-split static, 3 rolled (run-time K),
  * 4 fused with slab output (whole-sector stores), 5 dimension-in-lane (one unrolled body per chain length), 6 dimension-in-lane
  * with a run-time chain length (one body per polynomial order), 7 row-cooperative (16 lanes per trajectory-half; small
- * launches of long chains).  Negative: mtg_status.                                                                     */
+ * launches of long chains).  The answer is the launcher's own decision (one pure function, csrc/mtg_launch_plan.h, that
+ * the solve call runs as well), not a restatement of it.  Negative: mtg_status.                                         */
 int mtg_plan_launch_form(const mtg_plan* plan, int64_t batch, const mtg_layout* layout, uint32_t flags);
 void mtg_layout_aos(const mtg_plan* plan, int64_t batch, mtg_layout* out);
 void mtg_layout_soa(const mtg_plan* plan, int64_t batch, mtg_layout* out);

@@ -92,23 +92,23 @@ int mtg_context_set_option(mtg_context* ctx, const char* name, int value) {
   if (!ctx || !name) return MTG_ERR_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lock(ctx->mu);
   const std::string n(name);
-  if (n == "force_dg") ctx->knob_force_dg = value;
-  else if (n == "prefer_rolled") ctx->knob_prefer_rolled = value != 0;
-  else if (n == "no_dimlane") ctx->knob_no_dimlane = value != 0;
-  else if (n == "no_slab") ctx->knob_no_slab = value != 0;
-  else if (n == "no_queue") ctx->knob_no_queue = value != 0;
-  else if (n == "no_slab_extra") ctx->knob_no_slab_extra = value != 0;
-  else if (n == "no_dl_extra") ctx->knob_no_dl_extra = value != 0;
-  else if (n == "no_balance") ctx->knob_no_balance = value != 0;
-  else if (n == "dl_rt") ctx->knob_dl_rt = value;
-  else if (n == "dl_grid_per_cu") ctx->knob_dl_grid_per_cu = std::max(1, value);
+  if (n == "force_dg") ctx->knobs.force_dg = value;
+  else if (n == "prefer_rolled") ctx->knobs.prefer_rolled = value != 0;
+  else if (n == "no_dimlane") ctx->knobs.no_dimlane = value != 0;
+  else if (n == "no_slab") ctx->knobs.no_slab = value != 0;
+  else if (n == "no_queue") ctx->knobs.no_queue = value != 0;
+  else if (n == "no_slab_extra") ctx->knobs.no_slab_extra = value != 0;
+  else if (n == "no_dl_extra") ctx->knobs.no_dl_extra = value != 0;
+  else if (n == "no_balance") ctx->knobs.no_balance = value != 0;
+  else if (n == "dl_rt") ctx->knobs.dl_rt = value;
+  else if (n == "dl_grid_per_cu") ctx->knobs.dl_grid_per_cu = std::max(1, value);
   else if (n == "dl_any_sched_rr") ctx->knob_dl_any_rr = value != 0;
-  else if (n == "slab_policy") ctx->knob_slab_policy = value < 0 ? -1 : (value ? 1 : 0);
-  else if (n == "rolled_wg_per_cu") ctx->rolled_wg_per_cu = std::max(1, value);
-  else if (n == "dl_max_units") ctx->dl_max_units_per_cu = value;
+  else if (n == "slab_policy") ctx->knobs.slab_policy = value < 0 ? -1 : (value ? 1 : 0);
+  else if (n == "rolled_wg_per_cu") ctx->knobs.rolled_wg_per_cu = std::max(1, value);
+  else if (n == "dl_max_units") ctx->knobs.dl_max_units_per_cu = value;
   else if (n == "sample_generic") ctx->knob_sample_generic = value != 0;
   else if (n == "sample_max_blocks") ctx->knob_sample_max_blocks = std::max(0, value);
-  else if (n == "coop") ctx->knob_coop = value;
+  else if (n == "coop") ctx->knobs.coop = value;
   else if (n == "extrema_split") ctx->knob_extrema_split = value;
   else return set_err(ctx, MTG_ERR_INVALID_ARGUMENT, "unknown option: " + n);
   return MTG_OK;

@@ -1,5 +1,5 @@
 // mtg_abi_internal.h -- what the translation units behind the C ABI of include/mtg_hip.h share (host only, no kernels):
-//   mtg_abi.hip (context, device memory, layouts), mtg_plan.hip (rank decision, plans), mtg_dispatch.hip (form choice, launchers,
+//   mtg_abi.hip (context, device memory, layouts), mtg_plan.hip (rank decision, plans), mtg_dispatch.hip (launcher of mtg_launch_plan.h's decision,
 //   sequence / Mellinger / update / objective entries), mtg_shadow.hip (basic solution, refinement), mtg_multi.hip (mixed requests).
 #ifndef MTG_ABI_INTERNAL_H_
 #define MTG_ABI_INTERNAL_H_
@@ -17,6 +17,7 @@
 #include "../../include/mtg_hip.h"
 #include "mtg_kernels.h"
 #include "mtg_dimlane_rt.h"
+#include "mtg_launch_plan.h"
 
 int mtg_host_run(const MtgParams& P, int H, bool update);   // mtg_host.cpp: host build of the lane code
 // mtg_coop.hip: the row-cooperative kernel (0 launched, 1 shape / size not covered, 2 runtime error) and its LDS need
@@ -37,27 +38,12 @@ struct mtg_context {
   double* h_bounce = nullptr;
   size_t h_bounce_bytes = 0;
   int n_cu = 256;
-  // measurement knobs (A/B runs in tools/, form-forcing tests): set through mtg_context_set_option (include/mtg_hip_lab.h),
-  // never read from the environment by the library; defaults = the shipped behaviour.  The names in the comments are the
-  // environment variables the PYTHON layer forwards (mav_trajectory_generation_amd.Context) -- e.g. MTG_FORCE_DG -> "force_dg"
-  int knob_force_dg = 0;        // MTG_FORCE_DG: dimension-group size of the specialised kernels
-  bool knob_prefer_rolled = false;   // MTG_PREFER_ROLLED: rolled variant even where a static one exists
-  bool knob_no_dimlane = false;      // MTG_NO_DIMLANE: never pick the dimension-in-lane form
-  int dl_max_units_per_cu = -1;      // MTG_DL_MAX_UNITS: overrides the variants' upper limit (workgroups <= this x CUs; 0: none)
-  bool knob_no_slab = false;         // MTG_NO_SLAB: fused form without the slab-output kernel
-  bool knob_no_slab_extra = false;   // MTG_NO_SLAB_EXTRA: extra outputs (cost / d_P) through the older fused kernel
-  bool knob_no_dl_extra = false;     // MTG_NO_DL_EXTRA: extra outputs never through the dimension-in-lane kernels
-  bool knob_no_queue = false;        // MTG_NO_QUEUE: mtg_solve_linear_sequence as one launch per batch
-  int knob_dl_grid_per_cu = 8;       // MTG_DL_GRID_PER_CU: workgroups per CU of a (non-workspace) dimension-in-lane launch
-  int knob_dl_rt = -1;               // MTG_DL_RT: 1 = the run-time-K body even where a static variant exists, 0 = never (default: where none exists)
+  MtgKnobs knobs;                    // the form-related measurement knobs (mtg_launch_plan.h), set through mtg_context_set_option
+  // the other knobs (same rules: include/mtg_hip_lab.h, never read from the environment by the library)
   bool knob_dl_any_rr = false;       // MTG_DL_ANY_SCHED=rr: round 2's unit schedule of the cross-structure launch
-  bool knob_no_balance = false;      // MTG_NO_BALANCE: persistent grids are not evened out over their rounds
-  int knob_slab_policy = -1;         // MTG_SLAB_POLICY: 0 write-back, 1 nt sc1
-  int rolled_wg_per_cu = 4;          // MTG_ROLLED_WG_PER_CU: persistent workgroups per CU of the rolled (workspace) kernels
   bool knob_sample_generic = false;  // MTG_SAMPLE_GENERIC: mtg_sample_range never through its LDS-staged kernel
   int knob_sample_max_blocks = 0;    // MTG_SAMPLE_MAX_BLOCKS: >= 1 caps the persistent grid of mtg_sample_range (0: occupancy x CUs, the shipped grid)
   int knob_extrema_split = -1;       // MTG_EXTREMA_SPLIT: lanes per root search of the extrema kernels (include/mtg_hip_lab.h; -1: default)
-  int knob_coop = -1;                // MTG_COOP: 1 always / 0 never take the row-cooperative form where eligible (default: by size)
   // MTG_FLAG_CONCURRENT_ITEMS requests: side streams (created on first use) + fork / join events
   std::vector<hipStream_t> side_streams;
   hipEvent_t fork_event = nullptr;
@@ -81,17 +67,10 @@ struct mtg_context {
   std::mutex mu;
 };
 
+// one enqueued launch of the last solve: what mtg_launch_plan decided, the kernel parameters it ran with (params.ws: its workspace)
 struct LaunchRecord {
-  bool valid = false;
-  SolveFn fn = nullptr;
+  MtgLaunch launch;
   MtgParams params;
-  int ntiles = 0, grid = 0, gridy = 1;
-  size_t lds = 0;
-  const MtgDimlaneEntry* dl = nullptr;   // dimension-in-lane launch (mtg_dimlane.h): uses params.{times,dfix,coeffs,status,tstatus,B}
-  const MtgDimlaneRtEntry* rt = nullptr; // run-time-K dimension-in-lane launch (mtg_dimlane_rt.h)
-  int dl_aos = 0;                        // input layout kind of a dimension-in-lane launch (dimlane_input_kind)
-  bool coop = false;                     // row-cooperative launch (mtg_coop.hip)
-  double* dl_ws = nullptr;
 };
 
 struct mtg_plan {
@@ -102,13 +81,8 @@ struct mtg_plan {
   int n_fixed = 0, n_free = 0;
   int null_dim = 0;                 // STRUCTURAL rank deficiency of the free system R_PP (mtg_plan.hip: structural_null_dim)
   int* d_tables = nullptr;          // vmask | offF | offP
-  const MtgStaticEntry* fast = nullptr;        // all dimensions in one workgroup
-  const MtgStaticEntry* fast_split = nullptr;  // smallest dimension group that divides D
-  const MtgDimlaneEntry* dimlane = nullptr;    // dimension-in-lane form (canonical SoA inputs, coefficient output only)
-  const MtgDimlaneRtEntry* dimlane_rt = nullptr;   // run-time-K dimension-in-lane body (mtg_dimlane_rt.h): any chain length of the standard shapes
-  bool slab_attr_set[2] = {false, false};      // LDS attribute of the slab-output kernels set
-  bool slab_queue_attr_set = false;
-  bool slab_extra_attr_set = false;
+  MtgPlanForms forms;               // the table entries of the shape, resolved once (mtg_launch_plan.h)
+  bool lds_attr_set[4] = {false, false, false, false};   // [MtgLdsAttr]: LDS attribute of the slab-output kernels set
   double* ws = nullptr;
   size_t ws_bytes = 0;
   double* pert_cost = nullptr;      // [(K + 1)][batch] costs of mtg_mellinger_cost_gradient's virtual problems
@@ -180,32 +154,13 @@ inline void fill_common(const mtg_plan* p, MtgParams& P, int64_t batch, const mt
 }
 
 struct PerturbedTimes { double h, lower_bound; };   // mtg_mellinger_cost_gradient: (K + 1) virtual problems per trajectory
-// ---- one solve / update call: stage (host pointers) -> pick_form -> launch_<form> -> fetch (host pointers) ------------------
-enum class SolveForm { kUpdate, kCoop, kDimlaneRt, kDimlane, kFused };   // kFused: slab-output / static / rolled / generic kernels
-struct SolveCall {                  // everything a launcher needs, assembled once by mtg_solve_impl
-  mtg_plan* p;
-  int64_t batch;
-  const mtg_layout* L;
-  uint32_t flags;
-  bool cost_only, wc;               // wc: extra outputs (cost and / or d_P) requested
-  const PerturbedTimes* pert;
-  hipStream_t st;
-  MtgParams P;                      // device pointers, strides, tables
-  int ntiles;                       // 64-trajectory tiles (x (K + 1) virtual problems for perturbed-time launches)
-  int32_t* dts;                     // per-trajectory status on the device (or null)
-  const MtgDimlaneRtEntry* rt = nullptr;    // set by pick_form for the form it chose
-  const MtgDimlaneEntry* dl = nullptr;
-};
 
-// rows of a SoA buffer padded to the next multiple of 16 trajectories (mtg_layout_soa_padded)
-inline int64_t mtg_padded16(int64_t batch) { return (batch + 15) & ~(int64_t)15; }
 // contiguous [B][D][n] strides of a layout's fixed / free values
 inline void mtg_fixed_contiguous(mtg_layout* L, int D, int n) { L->fixed_stride_b = (int64_t)D * n; L->fixed_stride_d = n; L->fixed_stride_c = 1; }
 inline void mtg_free_contiguous(mtg_layout* L, int D, int n) { L->free_stride_b = (int64_t)D * n; L->free_stride_d = n; L->free_stride_c = 1; }
 
 // ---- functions that cross the translation units -------------------------------------------------------------------------------
 int mtg_status_code(mtg_context* ctx, int status_word);                                   // mtg_abi.hip: flags -> error code + text
-int mtg_dimlane_input_kind(const mtg_plan* p, const mtg_layout* L, int64_t batch);        // mtg_dispatch.hip
 // mtg_dispatch.hip: one solve / update call.  own_status_dev: a device status word of the CALL (zeroed here) instead of the
 // context's -- flags of earlier asynchronous launches stay where the next mtg_context_sync finds them; explicit_rhs
 // (MTG_FLAG_REFINE's correction solve; with MTG_FLAG_GENERIC_KERNEL): [batch][D][n_free], added to the right-hand side

@@ -337,14 +337,5 @@ __global__ __launch_bounds__(2 * kWave, 1) void mtg_solve_dl_rt_kernel(const dou
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-// table entry of the run-time-K bodies (one per polynomial order / dimension count): mtg_dimlane_rt.hip
-struct MtgDimlaneRtEntry {
-  int h, ms, mi, me, dv, dl;
-  int tpw, r_steps, l_steps;
-  size_t lds;
-  size_t step_bytes_per_lane;   // workspace bytes per head step and resident lane
-  int (*launch)(void* stream, int grid, const double* times, const double* dfix, double* coeffs, int* status, int* traj_status,
-                int B, int K, int ntiles, double* ws, int aos);
-};
 const MtgDimlaneRtEntry* mtg_find_dimlane_rt(int h, int dl, int k, int deriv, const int* mask);
 #endif  // MTG_DIMLANE_RT_H_

@@ -3,15 +3,13 @@
 #define MTG_KERNELS_H_
 #include <hip/hip_runtime.h>
 
+#include "mtg_entries.h"
 #include "mtg_lane.h"
 #include "mtg_slab.h"
 
 #ifndef MTG_STORE_AUX
 #define MTG_STORE_AUX 0   // cache-policy bits of the coefficient stores (16 = sc1 write-through; A/B knob)
 #endif
-
-constexpr int kWave = 64;
-constexpr int kBlock = 2 * kWave;  // wave 0: direction A (forward), wave 1: direction B
 
 // Coefficient output staged through LDS.  Each lane drops the D*N coefficients of the segment it
 // just recovered into its row of the wave's staging buffer (ds_write_b128, row stride an odd number
@@ -217,14 +215,7 @@ __host__ __device__ constexpr size_t mtg_slab_lds_bytes() {
 // layout; the persistent workgroups walk the tiles of all of them (tile -> (batch, tile inside the batch), batch-major), so
 // a wave of batch i + 1 starts the moment a SIMD is free -- no drain / launch gap between the batches (1.0-1.3 us between
 // dependent launches; ~1.8k cycles of store acknowledgement at the end of each) and the store tail of batch i runs under
-// the forward chains of batch i + 1.  The pointer triples travel in the kernel arguments (no upload in front of the launch).
-struct MtgSeqItem { const double* times; const double* dfix; double* coeffs; };
-constexpr int kSeqMax = 96;    // batches per launch (kernel arguments <= 4 KB); longer queues are cut into several launches
-struct MtgSeqQueue {
-  int n, tiles_per_batch;
-  MtgSeqItem item[kSeqMax];
-};
-
+// the forward chains of batch i + 1.  The pointer triples travel in the kernel arguments (MtgSeqQueue, mtg_entries.h).
 template <class C, int AUX, bool QUEUE, int OUT = 0>
 __device__ __forceinline__ void mtg_solve_slab_body(const MtgParams& P, int ntiles, const MtgSeqQueue* q) {
   static_assert(C::kStatic && C::KT >= 2 && !C::kPert, "slab-output form: static configurations, K >= 2");
@@ -433,55 +424,15 @@ __global__ __launch_bounds__(kWave) void mtg_update_slab_kernel(MtgParams P, int
   }
 }
 
-using SolveFn = void (*)(MtgParams, int);
-using UpdateFn = void (*)(MtgParams, int);
-using SolveMultiFn = void (*)(const MtgParams*, const MtgTileRef*, int);
 template <int H, int D> using GenericCfg = MtgCfg<H, D, 0, 0, 0, 0>;
 template <int H, int D> using GenericCostCfg = MtgCfg<H, D, 0, 0, 0, 0, 0, 1>;   // cost-only launches: perturbed-time capable
 
 // per-TU pickers (mtg_generic_hN.hip, mtg_static.hip)
 SolveFn mtg_pick_generic_solve(int h, int d, int out_mode);   // out_mode: 0 plain, 1 extra outputs (OUT 3), 2 cost only (OUT 9)
 UpdateFn mtg_pick_generic_update(int h, int d, bool with_cost);
-struct MtgStaticEntry {
-  int h, d, k, ms, mi, me, dv;
-  int heavy;       // static variant that spills: prefer a rolled variant for large launches
-  SolveFn fn[5];   // [extra outputs (cost / d_free)] + 2 * [write-through stores]; [4] = cost only (OUT 9)
-  void (*upd[2])(MtgParams, int);   // rolled entries: setFreeConstraints kernel [with cost]; static entries: null
-  void (*upd_slab[2][2])(MtgParams, int);   // rolled entries with all plan dimensions: the same with whole-sector output, [with cost][piece not a multiple of 64 bytes]
-  size_t upd_slab_lds;
-  SolveMultiFn multi[4];            // rolled entries: several plans in one launch, [extra outputs] + 2 * [write-through]
-};
 const MtgStaticEntry* mtg_find_static(int h, int d, int k, int deriv, const int* mask, bool rolled_only = false);
-using SolveQueueFn = void (*)(MtgParams, int, MtgSeqQueue);
-struct MtgSlabEntry {
-  int h, d, k, ms, mi, me, dv;
-  size_t lds;
-  SolveFn fn[2];   // coefficient store policy: [0] write-back, [1] nt sc1
-  SolveQueueFn queue;   // the same (nt sc1) over a queue of batches: mtg_solve_linear_sequence
-  SolveFn extra;        // nt sc1 with the extra outputs (OUT = 3: cost and / or d_P), round 3
-};
 const MtgSlabEntry* mtg_find_slab(int h, int d, int k, int deriv, const int* mask);
 
-// dimension-in-lane launch form (mtg_dimlane.h / mtg_dimlane.hip): canonical SoA inputs, coefficient output (+ status)
-struct MtgDimlaneEntry {
-  int h, k, ms, mi, me, dv, dl, np;
-  int tpw;            // trajectories per wave (64 / dl)
-  int lo_per_cu, hi_per_cu;   // default form while lo * CUs <= workgroups <= hi * CUs / 2 (hi = 0: no upper limit; hi counts HALF workgroups per CU)
-  size_t lds;         // dynamic LDS per workgroup
-  size_t ws_per_lane; // long-chain variants (MtgCfg::WSJ > 0): workspace bytes per resident lane (grid * np * 128 lanes), else 0
-  // enqueues one launch on `stream` (a hipStream_t): grid workgroups of np * 128 threads (coefficient stores: nt sc1); aos: input
-  // layout (0 canonical SoA, 1 canonical AoS, 2 padded SoA); returns 0 or -1 (attribute / launch set-up failed)
-  int (*launch)(void* stream, int grid, const double* times, const double* dfix, double* coeffs, int* status,
-                int* traj_status, int B, int ntiles, double* ws, int aos);
-  // a queue of batches in one launch (mtg_solve_linear_sequence; main-table variants only, else null): ntiles = tiles of
-  // all batches (q->n * q->tiles_per_batch)
-  int (*launch_queue)(void* stream, int grid, const MtgSeqQueue* q, int* status, int B, int ntiles, double* ws, int aos);
-  // solves that also return the cost and / or d_P (either pointer may be null; cost zeroed by the caller; ps_*: d_P strides
-  // in doubles); main-table variants only, else null
-  int (*launch_extra)(void* stream, int grid, const double* times, const double* dfix, double* coeffs, int* status,
-                      int* traj_status, int B, int ntiles, double* ws, int aos, double* dfree, double* cost, long long ps_b,
-                      long long ps_d, long long ps_c);
-};
 // MTG_FLAG_REFINE (mtg_refine.hip): r = -(R_PP x + R_PF d_F) in double-double for every trajectory and dimension ([B][D][n_free],
 // contiguous), and x += delta over the free slots; 0 or -1 (launch failed)
 int mtg_refine_residual_launch(void* stream, int H, int K, int D, int deriv, int h1off, const int* d_vmask, const int* d_offF,

@@ -192,14 +192,15 @@ static bool dl_any_schedule_on_device(mtg_context* ctx, MtgDlAnyGroup& g, const 
 static int multi_plan_dl_any(mtg_multi* m, uint32_t flags, std::vector<char>& taken) {
   mtg_context* ctx = m->ctx;
   const std::vector<mtg_multi_item>& items = m->items;
-  if ((flags & (MTG_FLAG_FUSED_DIMS | MTG_FLAG_SPLIT_DIMS | MTG_FLAG_GENERIC_KERNEL)) || ctx->knob_no_dimlane) return MTG_OK;
+  if ((flags & (MTG_FLAG_FUSED_DIMS | MTG_FLAG_SPLIT_DIMS | MTG_FLAG_GENERIC_KERNEL)) || ctx->knobs.no_dimlane) return MTG_OK;
   std::vector<int> cand;
   for (int i = 0; i < (int)items.size(); ++i) {
     const mtg_multi_item& it = items[(size_t)i];
     const mtg_plan* p = it.plan;
-    if (it.batch <= 0 || it.cost || (it.d_free && p->n_free > 0) || mtg_dl_any_index(p->dimlane) < 0) continue;
-    { const int kind = mtg_dimlane_input_kind(p, &it.layout, it.batch); if (kind < 0 || kind > 1) continue; }   // (padded SoA: single / queue launches only)
-    if (it.batch * 8 * (int64_t)std::max(p->K, p->n_fixed * p->D) >= (1ll << 32)) continue;
+    if (it.batch <= 0 || it.cost || (it.d_free && p->n_free > 0) || mtg_dl_any_index(p->forms.dimlane) < 0) continue;
+    { const int kind = mtg_input_kind(p->forms, &it.layout, it.batch); if (kind < 0 || kind > 1) continue; }   // (padded SoA: single / queue launches only)
+    // (the batch as it is, not its padded row stride: a recorded difference from the single launch's check, kept as it is)
+    if (!mtg_dl_offsets_fit(p->forms, it.batch, false)) continue;
     cand.push_back(i);
   }
   if (cand.size() < 2) return MTG_OK;
@@ -211,9 +212,9 @@ static int multi_plan_dl_any(mtg_multi* m, uint32_t flags, std::vector<char>& ta
   for (size_t bi = 0; bi < cand.size(); ++bi) {
     const mtg_multi_item& it = items[(size_t)cand[bi]];
     taken[(size_t)cand[bi]] = 1;
-    g.h_items[bi] = MtgDlAnyItem{it.times, it.d_fixed, it.coeffs, (int)it.batch, mtg_dl_any_index(it.plan->dimlane),
-                                 mtg_dimlane_input_kind(it.plan, &it.layout, it.batch), 0};
-    sched[bi] = MtgScheduleItem{it.plan->K, it.plan->H, (int)mtg_ceil_div(it.batch, it.plan->dimlane->tpw)};
+    g.h_items[bi] = MtgDlAnyItem{it.times, it.d_fixed, it.coeffs, (int)it.batch, mtg_dl_any_index(it.plan->forms.dimlane),
+                                 mtg_input_kind(it.plan->forms, &it.layout, it.batch), 0};
+    sched[bi] = MtgScheduleItem{it.plan->K, it.plan->H, (int)mtg_tiles(it.batch, it.plan->forms.dimlane->tpw)};
     g.nunits += sched[bi].tiles;
   }
   g.grid = std::min(g.nunits, ctx->n_cu * 2);      // two 2-wave workgroups per CU: one wave per SIMD
@@ -252,7 +253,7 @@ static void multi_group_rolled(mtg_multi* m, const std::vector<char>& taken) {
   for (int i = 0; i < (int)items.size(); ++i) {
     if (taken[(size_t)i]) continue;
     mtg_plan* p = items[(size_t)i].plan;
-    const MtgStaticEntry* e = (items[(size_t)i].batch > 0 && p->K >= 2) ? mtg_find_static(p->H, p->D, p->K, p->deriv, p->mask.data(), true) : nullptr;
+    const MtgStaticEntry* e = (items[(size_t)i].batch > 0 && p->K >= 2) ? p->forms.rolled : nullptr;
     if (!e || !e->multi[0]) {
       if (items[(size_t)i].batch > 0) m->singles.push_back(i);
       continue;
@@ -296,13 +297,13 @@ static int multi_upload_group(mtg_multi* m, MtgMultiGroup& g, uint32_t flags, lo
   std::vector<int> order(g.items.begin(), g.items.end());
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return item_work(items[(size_t)a]) > item_work(items[(size_t)b]); });
   // few tiles: the one-dimension-per-workgroup form of the same configurations (D x the workgroups, lighter waves)
-  // while all of them are resident at once -- the same rule as for single-plan launches (flags override)
-  const bool want_split = D > 1 && ((flags & MTG_FLAG_SPLIT_DIMS) || (!(flags & MTG_FLAG_FUSED_DIMS) && total_tiles * D <= 4ll * ctx->n_cu));
+  // while all of them are resident at once -- the rule of single-plan launches (flags override)
+  const bool want_split = D > 1 && ((flags & MTG_FLAG_SPLIT_DIMS) || (!(flags & MTG_FLAG_FUSED_DIMS) && mtg_all_resident(total_tiles, D, ctx->n_cu)));
   std::vector<const MtgStaticEntry*> ent(order.size());
   bool split_ok = want_split;
   for (size_t bi = 0; bi < order.size(); ++bi) {
     const mtg_plan* p = items[order[bi]].plan;
-    ent[bi] = mtg_find_static(p->H, p->D, p->K, p->deriv, p->mask.data(), true);
+    ent[bi] = p->forms.rolled;
     const MtgStaticEntry* es = want_split ? mtg_find_static(p->H, 1, p->K, p->deriv, p->mask.data(), true) : nullptr;
     if (!es || !es->multi[0] || (g.any && mtg_any_cfg_index(es) < 0)) split_ok = false;
   }
@@ -325,15 +326,14 @@ static int multi_upload_group(mtg_multi* m, MtgMultiGroup& g, uint32_t flags, lo
   for (size_t bi = 0; bi < order.size(); ++bi) {
     const mtg_multi_item& it = items[order[bi]];
     const int H = it.plan->H;
-    const int nt = (int)mtg_ceil_div(it.batch, kWave);
+    const int nt = (int)mtg_tiles(it.batch, kWave);
     const int cfg = g.any ? mtg_any_cfg_index(ent[bi]) : 0;
     for (int t = 0; t < nt; ++t) tiles.push_back(MtgTileRef{(int)bi, t, cfg});
     kc_max = std::max(kc_max, (it.plan->K + 1) / 2);
     g.extra = g.extra || it.cost != nullptr || (it.d_free != nullptr && it.plan->n_free > 0);
     E = std::max(E, (size_t)H * H + (size_t)Dw * H);
     const int fm = H - __builtin_popcount((unsigned)ent[bi]->mi);
-    const size_t stage = (size_t)64 * ((size_t)(Dw * 2 * H / 2) | 1) * 2 * sizeof(double);
-    g.lds = std::max(g.lds, 2 * stage + (size_t)2 * (fm * (fm + 1) / 2 + Dw * fm) * kWave * sizeof(double));
+    g.lds = std::max(g.lds, mtg_solve_lds_bytes(Dw, 2 * H, fm));
   }
   g.ntiles = (int)tiles.size();
   g.grid = std::min(g.ntiles, std::max(1, ctx->n_cu * 4 / g.ngroups));
@@ -386,7 +386,7 @@ int mtg_multi_create(mtg_context* ctx, int32_t n_items, const mtg_multi_item* it
     if (rc == MTG_OK) multi_group_rolled(m, taken);
     long long total_tiles = 0;
     for (const MtgMultiGroup& g : m->groups)
-      for (int i : g.items) total_tiles += mtg_ceil_div(m->items[(size_t)i].batch, kWave);
+      for (int i : g.items) total_tiles += mtg_tiles(m->items[(size_t)i].batch, kWave);
     for (size_t gi = 0; gi < m->groups.size() && rc == MTG_OK; ++gi) rc = multi_upload_group(m, m->groups[gi], flags, total_tiles);
   }
   if (rc != MTG_OK) {      // the one cleanup path: everything allocated so far belongs to m
@@ -417,7 +417,7 @@ static int multi_solve_body(mtg_multi* m) {
         if (it.cost) MTG_HIP_TRY(ctx, hipMemsetAsync(it.cost, 0, it.batch * sizeof(double), ctx->stream));
       }
       // few tiles: write-through stores (no serial end-of-kernel L2 write-back), as for single-plan launches
-      const bool write_through = (long long)g.ntiles * g.ngroups * g.any_units <= 4ll * ctx->n_cu;
+      const bool write_through = mtg_all_resident(g.ntiles, g.ngroups * g.any_units, ctx->n_cu);
       const int variant = (g.extra ? 1 : 0) + (write_through ? 2 : 0);
       SolveMultiFn fn = g.any ? mtg_multi_any_fn(g.dg, variant) : g.entry->multi[variant];
       if (g.any && g.lds > 64 * 1024 && !g.attr_set[variant]) {

@@ -8,7 +8,6 @@
 #include <utility>
 #include <vector>
 
-inline long long mtg_ceil_div(long long n, long long per) { return (n + per - 1) / per; }   // tiles of `per` trajectories for a batch of n
 inline long long mtg_work_estimate(int K, int N) { return (long long)K * N * N; }           // work per trajectory ~ chain length x N^2
 
 struct MtgScheduleItem { int K, H, tiles; };   // one item of the cross-structure dimension-in-lane launch, in launch order

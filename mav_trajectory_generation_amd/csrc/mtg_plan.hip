@@ -2,6 +2,22 @@
 // a structurally rank-deficient pattern) and destruction, the plan queries.
 #include "mtg_abi_internal.h"
 
+// the generic kernels of a polynomial order (one translation unit each), resolved into the plan's MtgPlanForms
+#define MTG_DECL(H) SolveFn mtg_pick_generic_solve_h##H(int, int); UpdateFn mtg_pick_generic_update_h##H(int, bool);
+MTG_DECL(1) MTG_DECL(2) MTG_DECL(3) MTG_DECL(4) MTG_DECL(5) MTG_DECL(6)
+#undef MTG_DECL
+
+SolveFn mtg_pick_generic_solve(int h, int d, int extra) {
+  static SolveFn (*const pick[6])(int, int) = {mtg_pick_generic_solve_h1, mtg_pick_generic_solve_h2, mtg_pick_generic_solve_h3,
+                                               mtg_pick_generic_solve_h4, mtg_pick_generic_solve_h5, mtg_pick_generic_solve_h6};
+  return h >= 1 && h <= 6 ? pick[h - 1](d, extra) : nullptr;
+}
+UpdateFn mtg_pick_generic_update(int h, int d, bool wc) {
+  static UpdateFn (*const pick[6])(int, bool) = {mtg_pick_generic_update_h1, mtg_pick_generic_update_h2, mtg_pick_generic_update_h3,
+                                                 mtg_pick_generic_update_h4, mtg_pick_generic_update_h5, mtg_pick_generic_update_h6};
+  return h >= 1 && h <= 6 ? pick[h - 1](d, wc) : nullptr;
+}
+
 // STRUCTURAL rank deficiency of R_PP.  The cost 0.5 d^T R d = sum over segments of the integral of (p^(d))^2 (LIN:124-140) vanishes
 // exactly on the trajectories whose every segment is a polynomial of degree < d; interior vertices share all h >= d + 1
 // derivative slots (LIN:199-205), so those are ONE polynomial of degree < d over the whole trajectory, and the null space of R_PP
@@ -116,12 +132,27 @@ int mtg_plan_create(mtg_context* ctx, const mtg_plan_desc* desc, mtg_plan** out)
   p->n_free = p->offP[K + 1];
   std::vector<std::pair<int, int>> pins;
   p->null_dim = p->n_free > 0 ? structural_null_dim(p->H, K, d, p->mask, &pins) : 0;
-  p->fast = mtg_find_static(p->H, D, K, d, p->mask.data());
-  for (int dg = 1; dg < D && !p->fast_split; ++dg) {
-    if (D % dg == 0) p->fast_split = mtg_find_static(p->H, dg, K, d, p->mask.data());
+  // everything of the launch decision that depends on the plan alone (mtg_launch_plan.h): the only table searches of a plan's life
+  MtgPlanForms& f = p->forms;
+  const int* mask = p->mask.data();
+  f.H = p->H; f.D = D; f.K = K; f.n_fixed = p->n_fixed;
+  f.free_mid = p->H - __builtin_popcount((unsigned)mask[(K + 1) / 2]);
+  f.fast = mtg_find_static(p->H, D, K, d, mask);
+  for (int dg = 1; dg < D && !f.fast_split; ++dg) {
+    if (D % dg == 0) f.fast_split = mtg_find_static(p->H, dg, K, d, mask);
   }
-  p->dimlane = mtg_find_dimlane(p->H, D, K, d, p->mask.data());
-  p->dimlane_rt = mtg_find_dimlane_rt(p->H, D, K, d, p->mask.data());
+  f.rolled = mtg_find_static(p->H, D, K, d, mask, true);
+  for (int dg = 1; dg <= 4; ++dg) f.group[dg] = mtg_find_static(p->H, dg, K, d, mask);
+  f.slab = mtg_find_slab(p->H, D, K, d, mask);
+  f.dimlane = mtg_find_dimlane(p->H, D, K, d, mask);
+  f.dimlane_rt = mtg_find_dimlane_rt(p->H, D, K, d, mask);
+  f.coop_shape = mask[0] == full && mask[K] == full;
+  for (int v = 1; v < K; ++v) f.coop_shape = f.coop_shape && mask[v] == 1;
+  f.coop_lds = mtg_coop_lds_bytes(p->H, D, K);
+  for (int dc = 1; dc <= 4; ++dc) {
+    for (int mode = 0; mode < 3; ++mode) f.generic_solve[dc][mode] = mtg_pick_generic_solve(p->H, dc, mode);
+    for (int wc = 0; wc < 2; ++wc) f.generic_update[dc][wc] = mtg_pick_generic_update(p->H, dc, wc != 0);
+  }
   std::vector<int> tab;
   tab.insert(tab.end(), p->mask.begin(), p->mask.end());
   tab.insert(tab.end(), p->offF.begin(), p->offF.end());
@@ -191,7 +222,7 @@ int mtg_plan_get_info(const mtg_plan* p, mtg_plan_info* out) {
   out->n_all = p->N * p->K;
   out->n_fixed = p->n_fixed;
   out->n_free = p->n_free;
-  out->kernel_variant = p->fast ? (p->fast->k < 0 ? 3 : 1) : (p->fast_split ? 2 : 0);
+  out->kernel_variant = p->forms.fast ? (p->forms.fast->k < 0 ? 3 : 1) : (p->forms.fast_split ? 2 : 0);
   out->algorithmic_bytes_per_trajectory = 8ll * (p->K + (int64_t)p->D * p->n_fixed + (int64_t)p->K * p->D * p->N);
   return MTG_OK;
 }
