@@ -416,6 +416,60 @@ int mtg_check_input_feasibility_host(int32_t n_coeffs, int32_t n_segments, int32
                                      int32_t* trajectory_result, int32_t* first_failing_segment,
                                      int32_t* segment_result, double* segment_bounds);
 
+/* ---- next to the input check: batched half-plane / flight-corridor feasibility check ------------
+ * Replaces, for a batch, FeasibilityBase::checkHalfPlaneFeasibility(const Segment&) / (const Trajectory&) over
+ * half_plane_constraints_ (mav_trajectory_generation_ros/src/feasibility_base.cpp:109-154) and the HalfPlane helpers
+ * (:54-86): which trajectories stay strictly on the inner side of every plane of a set -- a room, a geofence, a
+ * per-segment safe-flight corridor.
+ * A plane is 4 doubles (nx, ny, nz, offset): UNIT normal pointing inwards, offset = point . normal.  The clearance of
+ * a segment at local time t is  n . p(t) - offset  over dimensions 0-2 (a 4th, yaw, dimension is ignored); a plane
+ * fails a segment iff the clearance is <= 0 at t = 0, t = T or a real root in [0, T] of the derivative of the projected
+ * polynomial sum_dim n_dim p_dim (Polynomial::computeMinMaxCandidates), isolated directly as in mtg_minmax_magnitude.
+ *   n_coeffs              1 .. 12 (odd counts and counts below 4 run zero-padded; N <= 2 has no interior candidates)
+ *   n_segments            1 .. 2^22 - 1
+ *   dimension             3 or 4; anything else: every trajectory infeasible at segment 0 with plane -1 and NaN
+ *                         clearances (the reference returns false before it looks at a plane)
+ *   times                 times[b * times_stride_b + k * times_stride_k]; strides >= 1, [B][K] or [K][B] without overlap;
+ *                         T <= 0: no interior candidates, both ends are still evaluated
+ *   planes                segment k of trajectory b uses the n_planes planes at planes + b * planes_stride_b +
+ *                         k * planes_stride_k (strides in doubles, >= 0): (0, 0) one set for everything
+ *                         (half_plane_constraints_), (0, 4 P) one cell per segment, (4 P K, 4 P) a corridor per trajectory
+ *   n_planes              1 .. 64
+ *   trajectory_feasible out [batch]; required: 1 / 0
+ *   first_failing_segment out optional [batch]: first segment in segment order with a failing plane, -1 if none
+ *   first_failing_plane   out optional [batch]: first plane in list order that fails that segment, -1 if none
+ *   segment_clearance     out optional [batch][K]: minimum clearance over ALL planes and candidates (no early exit,
+ *                         unlike the reference, which returns at the first failure)
+ *   trajectory_clearance  out optional [batch]: minimum over the segments
+ * Comparison and order are the reference's: `clearance <= 0` fails, so a NaN clearance does not fail (and does not
+ * enter the minimum; nothing but NaN: +infinity).  A plane whose normal equals the previous plane's or its negation,
+ * component by component (by value: +0 equals -0), reuses the previous plane's critical points: a bounding box costs
+ * three root searches.  The clearance is evaluated on the projected polynomial (one Horner chain): it differs from the
+ * reference's (p(t) - point) . n by rounding only, so a verdict can differ only where a clearance is within rounding of 0.
+ * Device pointers (planes included: normals are not verified); asynchronous on the context's stream, three launches,
+ * capturable.  Argument errors: MTG_ERR_INVALID_ARGUMENT, nothing enqueued.                                        */
+int mtg_check_half_plane_feasibility(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension,
+                                     int64_t batch, const double* coeffs, const double* times, int64_t times_stride_b,
+                                     int64_t times_stride_k, const double* planes, int32_t n_planes,
+                                     int64_t planes_stride_b, int64_t planes_stride_k, int32_t* trajectory_feasible,
+                                     int32_t* first_failing_segment, int32_t* first_failing_plane,
+                                     double* segment_clearance, double* trajectory_clearance);
+/* The same check with HOST pointers on the library's host build of the same code, synchronous; needs no context and
+ * no device.  Here the planes are readable: a normal with | |n|^2 - 1 | > 1e-9 is MTG_ERR_INVALID_ARGUMENT.          */
+int mtg_check_half_plane_feasibility_host(int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                                          const double* coeffs, const double* times, int64_t times_stride_b,
+                                          int64_t times_stride_k, const double* planes, int32_t n_planes,
+                                          int64_t planes_stride_b, int64_t planes_stride_k,
+                                          int32_t* trajectory_feasible, int32_t* first_failing_segment,
+                                          int32_t* first_failing_plane, double* segment_clearance,
+                                          double* trajectory_clearance);
+/* HalfPlane(point, normal) for n planes (feasibility_base.cpp:54-59): points [n][3], normals [n][3] (any length > 0,
+ * divided by their norm) -> out [n][4].  A zero or non-finite normal: MTG_ERR_INVALID_ARGUMENT.  Host pointers.       */
+int mtg_half_planes_from_points_normals(int32_t n, const double* points, const double* normals, double* out);
+/* HalfPlane::createBoundingBox(center, size) (:69-86) -> out [6][4], in its order and with its signs: per axis the
+ * minimum face (center - size / 2) with normal +e, then the maximum face (center + size / 2) with -e.  Host pointers. */
+int mtg_half_planes_bounding_box(const double* center, const double* size, double* out);
+
 /* ---- the time optimisers' objective with soft constraints ---------------------------------------
  * Replaces, for a batch, the callbacks PolynomialOptimizationNonLinear<N> hands to nlopt
  * (impl/polynomial_optimization_nonlinear_impl.h, NL below): objectiveFunctionTime (NL:556-615) and

@@ -130,7 +130,17 @@ EXPORTS = {
     "mtg_check_input_feasibility_host": (ctypes.c_int, [
         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
         ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p]),
-    "mtg_time_objective_params_init": (None, [ctypes.POINTER(TimeObjectiveParamsC)]),
+    "mtg_check_half_plane_feasibility": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
+        ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, c_double_p, c_double_p]),
+    "mtg_check_half_plane_feasibility_host": (ctypes.c_int, [
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
+        c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        c_double_p, c_double_p]),
+    "mtg_half_planes_from_points_normals": (ctypes.c_int, [ctypes.c_int32, c_double_p, c_double_p, c_double_p]),
+    "mtg_half_planes_bounding_box": (ctypes.c_int, [c_double_p, c_double_p, c_double_p]),
+    "mtg_time_objective_params_init":(None, [ctypes.POINTER(TimeObjectiveParamsC)]),
     "mtg_time_objective": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Layout), c_double_p, c_double_p, c_double_p,
                                           ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p, c_double_p,
                                           c_double_p]),

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import enum
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -352,6 +352,107 @@ def check_input_feasibility_host(coeffs, times, constraints: InputConstraints, t
     if single:
         return traj[0], first[0], seg[0], bounds[0]
     return traj, first, seg, bounds
+
+
+def half_planes(points, normals) -> np.ndarray:
+    """HalfPlane(point, normal) for n planes: points [n][3], normals [n][3] (any length > 0) -> [n][4] rows (unit normal,
+    offset = point . normal), the plane format of check_half_plane_feasibility.  A zero normal raises."""
+    lib = L.load()
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    normals = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+    if points.shape != normals.shape:
+        raise MtgError(-1, "one point per normal")
+    out = np.empty((points.shape[0], 4), dtype=np.float64)
+    _check(lib, lib.mtg_half_planes_from_points_normals(points.shape[0], points.ctypes.data, normals.ctypes.data, out.ctypes.data))
+    return out
+
+
+def bounding_box_half_planes(center, size) -> np.ndarray:
+    """HalfPlane::createBoundingBox(center, size) -> [6][4]: per axis the minimum face with +e, then the maximum face with -e."""
+    lib = L.load()
+    center = np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    size = np.ascontiguousarray(size, dtype=np.float64).reshape(3)
+    out = np.empty((6, 4), dtype=np.float64)
+    _check(lib, lib.mtg_half_planes_bounding_box(center.ctypes.data, size.ctypes.data, out.ctypes.data))
+    return out
+
+
+class HalfPlaneFeasibilityResult(NamedTuple):
+    """trajectory_feasible [B] int32 (1 / 0), first_failing_segment [B] int32 (-1: none), first_failing_plane [B] int32
+    (-1: none), segment_clearance [B][K] or None, trajectory_clearance [B] or None (minimum signed distance to the planes)."""
+    trajectory_feasible: object
+    first_failing_segment: object
+    first_failing_plane: object
+    segment_clearance: object
+    trajectory_clearance: object
+
+
+def _plane_strides(shape, bsz: int, k: int):
+    """[P][4]: one set for everything; [K][P][4]: one cell per segment; [B][K][P][4]: a corridor per trajectory."""
+    if len(shape) not in (2, 3, 4) or shape[-1] != 4:
+        raise MtgError(-1, "planes must be [P][4], [K][P][4] or [B][K][P][4]")
+    p = int(shape[-2])
+    if len(shape) >= 3 and shape[-3] != k or len(shape) == 4 and shape[0] != bsz:
+        raise MtgError(-1, "planes: the segment / batch axes must match coeffs")
+    return p, (4 * p * k if len(shape) == 4 else 0), (4 * p if len(shape) >= 3 else 0)
+
+
+def check_half_plane_feasibility(ctx: "Context", coeffs, times, planes, times_layout: str = "aos",
+                                 want_clearance: bool = True) -> HalfPlaneFeasibilityResult:
+    """Batched FeasibilityBase::checkHalfPlaneFeasibility(Trajectory): coeffs [B][K][D][N], times ([B][K] 'aos' / [K][B] 'soa')
+    and planes ([P][4], [K][P][4] or [B][K][P][4] rows of (unit normal, offset), see half_planes) as CUDA float64 tensors.
+    A plane fails a segment iff n . p(t) - offset <= 0 at t = 0, T or a critical point of the projection."""
+    import torch
+    bsz, k, dim, n = coeffs.shape
+    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
+    assert planes.is_cuda and planes.dtype == torch.float64 and planes.is_contiguous()
+    p, psb, psk = _plane_strides(tuple(planes.shape), bsz, k)
+    dev = coeffs.device
+    feas = torch.empty((bsz,), dtype=torch.int32, device=dev)
+    fseg = torch.empty((bsz,), dtype=torch.int32, device=dev)
+    fplane = torch.empty((bsz,), dtype=torch.int32, device=dev)
+    seg_c = torch.empty((bsz, k), dtype=torch.float64, device=dev) if want_clearance else None
+    traj_c = torch.empty((bsz,), dtype=torch.float64, device=dev) if want_clearance else None
+    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
+    cur = ctx._enter()
+    rc = ctx.lib.mtg_check_half_plane_feasibility(ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()),
+                                                  ctypes.c_void_p(times.data_ptr()), sb, sk, ctypes.c_void_p(planes.data_ptr()),
+                                                  p, psb, psk, ctypes.c_void_p(feas.data_ptr()), ctypes.c_void_p(fseg.data_ptr()),
+                                                  ctypes.c_void_p(fplane.data_ptr()),
+                                                  ctypes.c_void_p(seg_c.data_ptr()) if seg_c is not None else None,
+                                                  ctypes.c_void_p(traj_c.data_ptr()) if traj_c is not None else None)
+    ctx._leave(cur)
+    _check(ctx.lib, rc, ctx.handle)
+    return HalfPlaneFeasibilityResult(feas, fseg, fplane, seg_c, traj_c)
+
+
+def check_half_plane_feasibility_host(coeffs, times, planes, times_layout: str = "aos") -> HalfPlaneFeasibilityResult:
+    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
+    [B][K][D][N] or one trajectory [K][D][N] (then planes [P][4] or [K][P][4], results without the batch axis).  Normals
+    that are not of unit length raise."""
+    lib = L.load()
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    planes = np.ascontiguousarray(planes, dtype=np.float64)
+    single = coeffs.ndim == 3
+    if single:
+        coeffs, times = coeffs[None], times[None]
+    bsz, k, dim, n = coeffs.shape
+    if times.size != bsz * k:
+        raise MtgError(-1, "times must hold one value per segment")
+    p, psb, psk = _plane_strides(planes.shape, bsz, k)
+    feas = np.empty((bsz,), dtype=np.int32)
+    fseg = np.empty((bsz,), dtype=np.int32)
+    fplane = np.empty((bsz,), dtype=np.int32)
+    seg_c = np.empty((bsz, k), dtype=np.float64)
+    traj_c = np.empty((bsz,), dtype=np.float64)
+    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
+    rc = lib.mtg_check_half_plane_feasibility_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk, planes.ctypes.data,
+                                                   p, psb, psk, feas.ctypes.data, fseg.ctypes.data, fplane.ctypes.data,
+                                                   seg_c.ctypes.data, traj_c.ctypes.data)
+    _check(lib, rc)
+    res = HalfPlaneFeasibilityResult(feas, fseg, fplane, seg_c, traj_c)
+    return HalfPlaneFeasibilityResult(*[a[0] for a in res]) if single else res
 
 
 class Plan:
