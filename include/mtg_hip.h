@@ -482,7 +482,11 @@ int mtg_half_planes_bounding_box(const double* center, const double* size, doubl
  *                     (evaluateMaximumMagnitudeAsSoftConstraint NL:767-795 over computeMaximumOfMagnitude LIN:466-497).
  * Accepted derivatives: 1 .. N/2 - 1 -- continuous across vertices, so that the reference's candidate set (segment starts,
  * interior critical points, the end of the last segment) holds the true maximum; its own N - derivative - 1 > 0 check is
- * implied.  Values must be > 0.  dimension <= 4 (a lane keeps a segment's D x N coefficients in registers).             */
+ * implied.  Values must be > 0.  dimension <= 4 (a lane keeps a segment's D x N coefficients in registers).
+ * Non-finite coefficients (mtg_time_objective, mtg_magnitude_soft_cost and its host form alike): a NaN or Inf among the
+ * coefficients that a constrained derivative reads -- indices >= derivative of any segment and dimension -- makes that
+ * trajectory's maximum NaN and its violation NaN for that constraint, and its soft term maximum_cost (so does a magnitude
+ * that overflows from finite coefficients).  No other trajectory and no other constraint is affected.                   */
 #define MTG_MAX_MAGNITUDE_CONSTRAINTS 4
 enum { /* NonlinearOptimizationParameters::TimeAllocMethod */
   MTG_TIME_SQUARED = 0,
@@ -512,7 +516,7 @@ void mtg_time_objective_params_init(mtg_time_objective_params* params);
  *   objective  out [batch]; required.  +inf for a trajectory the solve flags (segment time <= 0, breakdown); the context's
  *                  flag is raised as for any solve (mtg_context_sync)
  *   components out optional [batch][3] = (cost_trajectory, cost_time, cost_soft)
- *   maxima     out optional [batch][n_constraints]
+ *   maxima     out optional [batch][n_constraints]; NaN by the non-finite rule above
  *   violations out optional [batch][n_constraints] = maximum - value (evaluateMaximumMagnitudeConstraint NL:745-763)
  * Device pointers; asynchronous on the context's stream.  The plan keeps 48 bytes of workspace per trajectory, grown by
  * the first call of a batch size (like mtg_mellinger_cost_gradient's): capture a call after one plain call of that size.
@@ -522,7 +526,8 @@ int mtg_time_objective(mtg_plan* plan, int64_t batch, const mtg_layout* layout, 
                        double* components, double* maxima, double* violations);
 /* The maxima + soft-cost stage alone on existing coefficients [batch][K][D][N] (getTotalCostWithSoftConstraints' third term):
  *   cost_soft out [batch]; required.  maxima required too here ([batch][n_constraints]: the search reduces into it);
- *   violations optional.  times[b * times_stride_b + k * times_stride_k] as in mtg_minmax_magnitude.                     */
+ *   violations optional.  times[b * times_stride_b + k * times_stride_k] as in mtg_minmax_magnitude.
+ *   Non-finite coefficients: the rule above (maximum and violation NaN, soft term maximum_cost, that trajectory only).   */
 int mtg_magnitude_soft_cost(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
                             const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
                             const mtg_time_objective_params* params, double* cost_soft, double* maxima, double* violations);

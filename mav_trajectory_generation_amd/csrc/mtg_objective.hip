@@ -7,7 +7,8 @@
 // derivative on them one after the other, so the searches share the two LDS root buffers ([slot][lane] layout, as in
 // mtg_extrema.hip).  Only the largest candidate value is kept; the lane folds it into its trajectory's slot with a 64-bit
 // atomic maximum on the BIT PATTERN -- magnitudes are non-negative, so unsigned order is numeric order, and the result does not
-// depend on which lane arrives first.  A lane per trajectory then forms the components (cost arithmetic: mtg_objective_lane.h).
+// depend on which lane arrives first; a NaN maximum (non-finite coefficients: mtg_objective_lane.h) is above every number in that
+// order and stays, whichever segment it comes from.  A lane per trajectory then forms the components (cost arithmetic: mtg_objective_lane.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>

@@ -3,6 +3,7 @@
 // (getTotalCostWithSoftConstraints' third term), and the CPU anchor of the device kernels.  Touches no device.
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 
 #include "../../include/mtg_hip.h"
 #include "mtg_objective_lane.h"
@@ -39,6 +40,16 @@ extern "C" int mtg_objective_constraints(const mtg_time_objective_params* in, mt
 
 namespace {
 
+// The device's fold (atomicMax on the bit pattern, mtg_objective.hip): magnitudes are >= +0, so unsigned order is numeric order,
+// and a NaN segment maximum -- whatever its sign bit -- is above every number and stays.  (std::fmax dropped it: a trajectory
+// of NaN coefficients reported maximum 0 and the best possible soft cost.)
+double fold_max(double best, double m) {
+  uint64_t a, b;
+  std::memcpy(&a, &best, sizeof a);
+  std::memcpy(&b, &m, sizeof b);
+  return b > a ? m : best;
+}
+
 template <int NC, int DC>
 void run(int N, int K, int D, int64_t B, const double* coeffs, const double* times, int64_t ts_b, int64_t ts_k,
          const mtgo::Constraints& con, const mtg_time_objective_params& par, double* cost_soft, double* maxima, double* violations) {
@@ -48,7 +59,7 @@ void run(int N, int K, int D, int64_t B, const double* coeffs, const double* tim
     double best[mtgo::kMaxConstraints] = {0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < K; ++k) {
       mtgo::segment_maxima<NC, DC, double*>(coeffs + (b * K + k) * (int64_t)(D * N), N, D, times[b * ts_b + k * ts_k], con, r,
-                                            [&best](int q, double m) { best[q] = std::fmax(best[q], m); });
+                                            [&best](int q, double m) { best[q] = fold_max(best[q], m); });
     }
     double soft = 0.0;
     for (int q = 0; q < con.n; ++q) {

@@ -81,7 +81,10 @@ MTGX_HD double magnitude_max(const double (&p)[DC][NC], double T, Roots& roots) 
   const int cnt = mtgx::real_roots_unit<L, Roots>(g, roots, base);
   double best = fmax(magnitude_at<NC, DC, DER>(p, 0.0), magnitude_at<NC, DC, DER>(p, T));
   for (int i = 0; i < cnt; ++i) best = fmax(best, magnitude_at<NC, DC, DER>(p, roots[base + i] * T));
-  return best;
+  // A NaN or Inf among the coefficients this derivative reads leaves no finite candidate: each value is NaN (fma(inf, 0, x) at
+  // t = 0) or +inf, and fmax drops a NaN beside an +inf.  Both are reported as NaN -- "no maximum" -- which the callers' folds
+  // keep (include/mtg_hip.h); so is a magnitude that overflows from finite coefficients.
+  return best < INFINITY ? best : NAN;
 }
 
 // One derivative order of one segment: searched if any constraint names it, and reported to each of them
