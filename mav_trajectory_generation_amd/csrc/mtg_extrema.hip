@@ -11,10 +11,7 @@
 // FP64-issue bound, not HBM bound: ~10^4 FMAs per lane against 240 B of coefficients read (round 4: two independent chains
 // at a time and lane-aligned refinement rounds, mtg_extrema_lane.h).  The two root buffers of each lane live in LDS ([slot][lane]
 // layout: lanes in lock-step hit distinct banks); everything else is in registers with compile-time indices.
-#include <hip/hip_runtime.h>
-
-#include "../../include/mtg_hip.h"
-#include "mtg_extrema_lane.h"
+#include "mtg_segment_kernel.h"
 
 extern "C" int mtg_context_extrema_split(const mtg_context* ctx);   // measurement knob "extrema_split" (mtg_hip_lab.h): -1 auto
 
@@ -23,24 +20,14 @@ namespace {
 constexpr int kThreads = 128;   // two root buffers of L - 1 doubles per lane in LDS: 128 x 2 x 21 x 8 B = 43 KB at most
 
 struct ExtremaParams {
-  const double* coeffs;   // [B][K][D][N]
-  const double* times;    // times[b*ts_b + k*ts_k]
-  long long ts_b, ts_k;
+  mtgs::SegShape s;
   double* seg_out;        // [n_slots][B][K][4]  (t_min, v_min, t_max, v_max), segment-local times
   double* traj_out;       // [n_slots][B][4]
   int* traj_seg;          // [n_slots][B][2] (segment of the minimum, of the maximum) or null
-  long long B;
-  int N, K, D;
   unsigned mask;
   int der[2];
   int split;              // lanes that share one root search (launch_seg): 1, 2 or 4
   int rolled;             // one code body for all levels of the derivative chain (mtg_extrema_lane.h, Level) or one per level
-};
-
-template <int COLS>
-struct LdsRoots {
-  double* p;   // the search's column: element i at p[i * COLS]
-  __device__ double& operator[](int i) { return p[i * COLS]; }
 };
 
 // SPLIT lanes share one (trajectory, segment) root search (mtg_extrema_lane.h, Share): a launch with about one wavefront per SIMD
@@ -51,19 +38,15 @@ struct LdsRoots {
 template <int NMAX, int SPLIT, bool ROLLED>
 __device__ __forceinline__ void mtg_minmax_seg_body(const ExtremaParams& P, double* lds) {
   constexpr int COLS = kThreads / SPLIT;
-  const long long total = P.B * P.K;
-  const long long idx = ((long long)blockIdx.x * kThreads + threadIdx.x) / SPLIT;
+  const mtgs::SegLane L = mtgs::seg_lane(P.s, ((long long)blockIdx.x * kThreads + threadIdx.x) / SPLIT);
   const int part = threadIdx.x % SPLIT;
-  if (idx >= total) return;
+  if (!L.in_range) return;
   const int slot = blockIdx.y;
-  const long long b = idx / P.K;
-  const int seg = (int)(idx - b * P.K);
-  const double T = P.times[b * P.ts_b + (long long)seg * P.ts_k];
-  LdsRoots<COLS> roots{lds + threadIdx.x / SPLIT};
-  const mtgx::MinMax mm = mtgx::segment_minmax<NMAX, LdsRoots<COLS>, ROLLED>(P.coeffs + idx * (long long)(P.D * P.N), P.N, P.D, P.mask,
-                                                                             P.der[slot], T, roots, mtgx::Share{part, part + 1, SPLIT});
+  mtgs::LdsColumn<COLS> roots{lds + threadIdx.x / SPLIT};   // the search's column
+  const mtgx::MinMax mm = mtgx::segment_minmax<NMAX, mtgs::LdsColumn<COLS>, ROLLED>(L.c, P.s.N, P.s.D, P.mask, P.der[slot], L.T, roots,
+                                                                                    mtgx::Share{part, part + 1, SPLIT});
   if (part != 0) return;
-  double* o = P.seg_out + ((long long)slot * total + idx) * 4;
+  double* o = P.seg_out + ((long long)slot * (P.s.B * P.s.K) + L.idx) * 4;
   reinterpret_cast<double2*>(o)[0] = make_double2(mm.t_min, mm.v_min);
   reinterpret_cast<double2*>(o)[1] = make_double2(mm.t_max, mm.v_max);
 }
@@ -86,23 +69,23 @@ __global__ __launch_bounds__(kThreads) void mtg_minmax_seg_kernel(ExtremaParams 
 // smaller / larger value wins.
 __global__ void mtg_minmax_traj_kernel(ExtremaParams P) {
   const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= P.B) return;
+  if (b >= P.s.B) return;
   const int slot = blockIdx.y;
-  const double* s = P.seg_out + ((long long)slot * P.B + b) * P.K * 4;
+  const double* s = P.seg_out + ((long long)slot * P.s.B + b) * P.s.K * 4;
   double t_min = 0.0, v_min = DBL_MAX, t_max = 0.0, v_max = -DBL_MAX;
   int k_min = 0, k_max = 0;
-  for (int k = 0; k < P.K; ++k) {
+  for (int k = 0; k < P.s.K; ++k) {
     const double2 lo = reinterpret_cast<const double2*>(s)[2 * k];
     const double2 hi = reinterpret_cast<const double2*>(s)[2 * k + 1];
     if (lo.y < v_min) { v_min = lo.y; t_min = lo.x; k_min = k; }
     if (hi.y > v_max) { v_max = hi.y; t_max = hi.x; k_max = k; }
   }
-  double* o = P.traj_out + ((long long)slot * P.B + b) * 4;
+  double* o = P.traj_out + ((long long)slot * P.s.B + b) * 4;
   reinterpret_cast<double2*>(o)[0] = make_double2(t_min, v_min);
   reinterpret_cast<double2*>(o)[1] = make_double2(t_max, v_max);
   if (P.traj_seg) {
-    P.traj_seg[((long long)slot * P.B + b) * 2 + 0] = k_min;
-    P.traj_seg[((long long)slot * P.B + b) * 2 + 1] = k_max;
+    P.traj_seg[((long long)slot * P.s.B + b) * 2 + 0] = k_min;
+    P.traj_seg[((long long)slot * P.s.B + b) * 2 + 1] = k_max;
   }
 }
 
@@ -184,8 +167,7 @@ __global__ void mtg_scale_finish_kernel(ScaleParams P) {
 template <int NMAX, int NMAX1 = NMAX>
 void launch_seg(const ExtremaParams& P, int n_slots, hipStream_t stream) {
   constexpr int L = 2 * NMAX - 2;
-  const long long total = P.B * P.K;
-  const dim3 grid((unsigned)((P.split * total + kThreads - 1) / kThreads), n_slots);
+  const dim3 grid(mtgs::grid_for(P.split * P.s.B * P.s.K, kThreads).x, n_slots);
   const size_t lds = (size_t)(kThreads / P.split) * 2 * (L - 1) * sizeof(double);   // two root buffers per search (mtg_extrema_lane.h)
 #define MTG_XL(S, R) hipLaunchKernelGGL((mtg_minmax_seg_kernel<NMAX, R ? NMAX : NMAX1, S, R>), grid, dim3(kThreads), lds, stream, P)
   if (P.rolled) {   // (measurement knob: one or two lanes, one bound for all slots)
@@ -213,16 +195,16 @@ int launch_minmax(ExtremaParams& P, int n_slots, hipStream_t stream, int option)
   // what bounds the kernel (its zero-padded chains cost more than the instruction fetches they save): per-level bodies stay.
   const int split_option = option < 0 ? 0 : (option & 3);
   P.rolled = option < 0 ? 0 : ((option & 4) ? 1 : 0);
-  const long long waves = (P.B * P.K + 63) / 64 * n_slots;   // at one lane per search, all derivative slots of the launch
+  const long long waves = (P.s.B * P.s.K + 63) / 64 * n_slots;   // at one lane per search, all derivative slots of the launch
   P.split = split_option == 3 ? 4 : (split_option != 0 ? split_option : (waves <= kFourLanesMaxWaves ? 4 : (waves <= kTwoLanesMaxWaves ? 2 : 1)));
   if (P.rolled && P.split == 4) P.split = 2;
   int n_d = 0;
   for (int s = 0; s < n_slots; ++s) {
-    const int nd = P.N - P.der[s];
+    const int nd = P.s.N - P.der[s];
     if (nd > n_d) n_d = nd;
   }
   // (velocity + acceleration of the time-scaling path: slot 1's polynomial is one coefficient shorter)
-  const bool shorter1 = n_slots == 2 && P.N - P.der[0] == n_d && P.N - P.der[1] == n_d - 1;
+  const bool shorter1 = n_slots == 2 && P.s.N - P.der[0] == n_d && P.s.N - P.der[1] == n_d - 1;
   if (n_d <= 7) launch_seg<7>(P, n_slots, stream);
   else if (n_d <= 8) { if (shorter1) launch_seg<8, 7>(P, n_slots, stream); else launch_seg<8>(P, n_slots, stream); }
   else if (n_d <= 9) { if (shorter1) launch_seg<9, 8>(P, n_slots, stream); else launch_seg<9>(P, n_slots, stream); }
@@ -230,7 +212,7 @@ int launch_minmax(ExtremaParams& P, int n_slots, hipStream_t stream, int option)
   else if (n_d <= 11) { if (shorter1) launch_seg<11, 10>(P, n_slots, stream); else launch_seg<11>(P, n_slots, stream); }
   else launch_seg<12>(P, n_slots, stream);
   if (P.traj_out)
-    hipLaunchKernelGGL(mtg_minmax_traj_kernel, dim3((unsigned)((P.B + 255) / 256), n_slots), dim3(256), 0, stream, P);
+    hipLaunchKernelGGL(mtg_minmax_traj_kernel, dim3(mtgs::grid_for(P.s.B, 256).x, n_slots), dim3(256), 0, stream, P);
   return hipGetLastError() == hipSuccess ? MTG_OK : MTG_ERR_DEVICE;
 }
 
@@ -244,8 +226,6 @@ int check_common(mtg_context* ctx, int n_coeffs, int n_segments, int dimension, 
 
 }  // namespace
 
-extern "C" int mtg_context_stream_device(mtg_context* ctx, void** stream, int* device);
-
 extern "C" int mtg_minmax_magnitude(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension,
                                     int64_t batch, const double* coeffs, const double* times, int64_t times_stride_b,
                                     int64_t times_stride_k, int32_t derivative, uint32_t dimension_mask,
@@ -258,17 +238,15 @@ extern "C" int mtg_minmax_magnitude(mtg_context* ctx, int32_t n_coeffs, int32_t 
   if (dimension_mask == 0) dimension_mask = all;
   if (dimension_mask & ~all) return MTG_ERR_INVALID_ARGUMENT;   // "dimensions out of bounds" (segment.cpp:102-107)
   if (batch == 0) return MTG_OK;
-  void* stream = nullptr;
-  int device = 0;
-  rc = mtg_context_stream_device(ctx, &stream, &device);
+  hipStream_t stream;
+  rc = mtgs::entry_stream(ctx, &stream);
   if (rc != MTG_OK) return rc;
-  if (hipSetDevice(device) != hipSuccess) return MTG_ERR_DEVICE;
   ExtremaParams P;
-  P.coeffs = coeffs; P.times = times; P.ts_b = times_stride_b; P.ts_k = times_stride_k;
+  P.s = {coeffs, times, times_stride_b, times_stride_k, batch, n_coeffs, n_segments, dimension};
   P.seg_out = segment_minmax; P.traj_out = trajectory_minmax; P.traj_seg = trajectory_minmax ? trajectory_segment_idx : nullptr;
-  P.B = batch; P.N = n_coeffs; P.K = n_segments; P.D = dimension; P.mask = dimension_mask;
+  P.mask = dimension_mask;
   P.der[0] = derivative; P.der[1] = derivative;
-  return launch_minmax(P, 1, (hipStream_t)stream, mtg_context_extrema_split(ctx));
+  return launch_minmax(P, 1, stream, mtg_context_extrema_split(ctx));
 }
 
 extern "C" int mtg_scale_segment_times_to_meet_constraints(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments,
@@ -280,17 +258,14 @@ extern "C" int mtg_scale_segment_times_to_meet_constraints(mtg_context* ctx, int
   if (rc != MTG_OK) return rc;
   if (!workspace || max_iterations < 1 || !(v_max > 0.0) || !(a_max > 0.0) || n_coeffs < 3) return MTG_ERR_INVALID_ARGUMENT;
   if (batch == 0) return MTG_OK;
-  void* stream = nullptr;
-  int device = 0;
-  rc = mtg_context_stream_device(ctx, &stream, &device);
+  hipStream_t stream;
+  rc = mtgs::entry_stream(ctx, &stream);
   if (rc != MTG_OK) return rc;
-  if (hipSetDevice(device) != hipSuccess) return MTG_ERR_DEVICE;
   ExtremaParams P;
-  P.coeffs = coeffs; P.times = times; P.ts_b = times_stride_b; P.ts_k = times_stride_k;
+  P.s = {coeffs, times, times_stride_b, times_stride_k, batch, n_coeffs, n_segments, dimension};
   P.seg_out = workspace;
   P.traj_out = workspace + (size_t)2 * batch * n_segments * 4;
   P.traj_seg = nullptr;
-  P.B = batch; P.N = n_coeffs; P.K = n_segments; P.D = dimension;
   P.mask = dimension >= 32 ? 0xffffffffu : ((1u << dimension) - 1u);   // "whatever dimensions we have" (trajectory.cpp:346-347)
   P.der[0] = 1;   // derivative_order::VELOCITY
   P.der[1] = 2;   // derivative_order::ACCELERATION
@@ -299,10 +274,10 @@ extern "C" int mtg_scale_segment_times_to_meet_constraints(mtg_context* ctx, int
   S.scaling = scaling; S.within = within_range; S.B = batch; S.N = n_coeffs; S.K = n_segments; S.D = dimension;
   S.v_max = v_max; S.a_max = a_max; S.max_iterations = max_iterations;
   // ONE root search (velocity and acceleration in one launch), then the whole check / stretch loop analytically (mtg_scale_loop)
-  rc = launch_minmax(P, 2, (hipStream_t)stream, mtg_context_extrema_split(ctx));
+  rc = launch_minmax(P, 2, stream, mtg_context_extrema_split(ctx));
   if (rc != MTG_OK) return rc;
   const long long total = (long long)batch * n_segments * dimension;
-  hipLaunchKernelGGL(mtg_scale_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, S);
-  hipLaunchKernelGGL(mtg_scale_finish_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, S);
+  hipLaunchKernelGGL(mtg_scale_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, S);
+  hipLaunchKernelGGL(mtg_scale_finish_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, stream, S);
   return hipGetLastError() == hipSuccess ? MTG_OK : MTG_ERR_DEVICE;
 }

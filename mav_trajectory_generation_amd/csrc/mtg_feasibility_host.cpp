@@ -81,12 +81,9 @@ extern "C" int mtg_check_input_feasibility_host(int32_t n_coeffs, int32_t n_segm
   if (mtg_feasibility_limits(constraints, &lim) != MTG_OK) return MTG_ERR_INVALID_ARGUMENT;
   if (!mtgf::arguments_ok(n_coeffs, n_segments, dimension, batch, times_stride_b, times_stride_k, lim))
     return MTG_ERR_INVALID_ARGUMENT;
-#define MTG_FH(NC) run<NC>(n_coeffs, n_segments, dimension, batch, coeffs, times, times_stride_b, times_stride_k, lim, \
-                           trajectory_result, first_failing_segment, segment_result, segment_bounds)
-  if (n_coeffs <= 6) MTG_FH(6);
-  else if (n_coeffs <= 8) MTG_FH(8);
-  else if (n_coeffs <= 10) MTG_FH(10);
-  else MTG_FH(12);
-#undef MTG_FH
+  mtgs::with_instance<6>(n_coeffs, [&](auto nc) {
+    run<decltype(nc)::value>(n_coeffs, n_segments, dimension, batch, coeffs, times, times_stride_b, times_stride_k, lim,
+                             trajectory_result, first_failing_segment, segment_result, segment_bounds);
+  });
   return MTG_OK;
 }

@@ -15,7 +15,7 @@
 // Same code runs on the device (mtg_feasibility.hip) and on the host (mtg_feasibility_host.cpp).
 #pragma once
 
-#include "mtg_extrema_lane.h"
+#include "mtg_segment_lane.h"
 
 namespace mtgf {
 
@@ -35,58 +35,25 @@ MTGX_HD bool has(double limit) { return limit == limit; }
 // what both entry points accept (include/mtg_hip.h)
 inline bool arguments_ok(int n_coeffs, int n_segments, int dimension, long long batch, long long ts_b, long long ts_k,
                          const Limits& lim) {
-  if (n_coeffs < kMinCoeffs || n_coeffs > mtgx::kMaxCoeffs || n_segments < 1 || dimension < 1 || dimension > 32 || batch < 0)
-    return false;
-  if (ts_b < 1 || ts_k < 1) return false;
-  // [B][K] with rows at least K apart, or [K][B] with rows at least B apart: anything else aliases two segments' times
-  if (!(ts_b >= (long long)n_segments * ts_k || ts_k >= batch * ts_b)) return false;
-  if (!(lim.min_section_time_s == lim.min_section_time_s) || !(lim.gravity == lim.gravity)) return false;
-  return true;
+  return mtgs::shape_ok(n_coeffs, kMinCoeffs, n_segments, dimension, 32, batch, ts_b, ts_k) &&
+         lim.min_section_time_s == lim.min_section_time_s && lim.gravity == lim.gravity;
 }
 
 // base(DER, i) of polynomial.cpp:145-160 as a compile-time-foldable product
 MTGX_HD double ff(int i, int der) { return mtgx::falling_factorial(i, der); }
 
-// || p^(DER)(t) + off || over dimensions 0-2 (Polynomial::evaluate: Horner from the highest power down; the offset joins the
-// constant term, as in the thrust segment's coefficients, feasibility_analytic.cpp:138-144)
+// || p^(DER)(t) + off || over dimensions 0-2
 template <int NC, int DER>
 MTGX_HD double magnitude3_at(const double (&p)[3][NC], const double (&off)[3], double t) {
-  double acc = 0.0;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    double r = 0.0;
-#pragma unroll
-    for (int i = NC - 1; i > DER; --i) r = fma(r, t, ff(i, DER) * p[d][i]);
-    r = fma(r, t, ff(DER, DER) * p[d][DER] + off[d]);
-    acc = fma(r, r, acc);
-  }
-  return sqrt(acc);
+  return mtgs::magnitude_at<NC, 3, DER, true>(p, off, t);
 }
 
-// real roots in tau = t / T in [0, 1] of the derivative of || p^(DER) + off ||^2 (the convolved polynomial of
-// segment.cpp:96-115): count returned, ascending at roots[base + i]
+// real roots in tau = t / T in [0, 1] of the derivative of || p^(DER) + off ||^2: count returned, ascending at roots[base + i]
 template <int NC, int DER, class Roots>
 MTGX_HD int magnitude3_roots(const double (&p)[3][NC], const double (&off)[3], double T, Roots& roots, int& base) {
-  constexpr int NQ = NC - DER;
-  constexpr int L = 2 * NQ - 2;
-  double g[L];
-#pragma unroll
-  for (int j = 0; j < L; ++j) g[j] = 0.0;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    double u[NQ];
-    double tp = 1.0;
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      u[i] = (p[d][i + DER] * ff(i + DER, DER) + (i == 0 ? off[d] : 0.0)) * tp;
-      tp *= T;
-    }
-#pragma unroll
-    for (int i = 0; i < NQ; ++i)
-#pragma unroll
-      for (int j = 0; j + 1 < NQ; ++j) g[i + j] = fma(u[i], (double)(j + 1) * u[j + 1], g[i + j]);
-  }
-  return mtgx::real_roots_unit<L, Roots>(g, roots, base);
+  double g[2 * (NC - DER) - 2];
+  mtgs::magnitude_derivative<NC, 3, DER, true>(p, off, T, g);
+  return mtgx::real_roots_unit<2 * (NC - DER) - 2, Roots>(g, roots, base);
 }
 
 // max(|min|, |max|) of y^(DER) over [0, T] (Polynomial::computeMinMax: end points + real roots of y^(DER+1))
@@ -171,10 +138,7 @@ MTGX_HD int segment_check(const double* c, int N, int D, double T, const Limits&
   for (int q = 0; q < kNumBounds; ++q) bounds[q] = NAN;
   if (!(D == 3 || D == 4)) return kIndeterminable;
   double p[3][NC];
-#pragma unroll
-  for (int d = 0; d < 3; ++d)
-#pragma unroll
-    for (int i = 0; i < NC; ++i) p[d][i] = i < N ? c[d * N + i] : 0.0;
+  mtgs::load_padded(c, N, D, p);
   const double zero[3] = {0.0, 0.0, 0.0};
   const double grav[3] = {0.0, 0.0, lim.gravity};
   const bool want_xy = has(lim.omega_xy_max);

@@ -11,50 +11,35 @@
 // minimum too, on the ORDER-MAPPED bits of the double (sign bit flipped for positive values, all bits for negative ones:
 // unsigned order = numeric order), so no scratch and no floating-point atomic on a signed value; a lane per trajectory then
 // decodes both words in place.
-#include <hip/hip_runtime.h>
-
-#include "../../include/mtg_hip.h"
 #include "mtg_halfplane_lane.h"
+#include "mtg_segment_kernel.h"
 
 namespace {
 
 // One wavefront per workgroup: the lanes never synchronise, and 10k x 8 segments are 1250 wavefronts for 1024 SIMDs, so the
 // smallest workgroup spreads them best.  Root buffers: 2 (N - 2) doubles per lane, 10 KB per workgroup at N = 12.
 constexpr int kThreads = 64;
-constexpr int kNoFailure = 0x7fffffff;
+using mtgs::kNoFailure;
 
 struct HpParams {
-  const double* coeffs;   // [B][K][D][N]
-  const double* times;    // times[b*ts_b + k*ts_k]
+  mtgs::SegShape s;
   const double* planes;   // planes + b*ps_b + k*ps_k: n_planes x (nx, ny, nz, offset)
-  long long ts_b, ts_k, ps_b, ps_k;
+  long long ps_b, ps_k;
   int* traj_word;         // [B]: kNoFailure, or min over failing segments of (segment << 8 | plane); decoded in place to 1 / 0
   int* first_segment;     // [B] or null
   int* first_plane;       // [B] or null
   double* seg_clearance;  // [B][K] or null
   double* traj_clearance; // [B] or null: holds the order-mapped minimum between init and decode
-  long long B;
-  int N, K, D, n_planes;
+  int n_planes;
 };
 
 __device__ unsigned long long order_key(double x) {
   const unsigned long long u = (unsigned long long)__double_as_longlong(x);
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
+constexpr unsigned long long kKeyInfinity = 0xfff0000000000000ull;   // order_key(+infinity): "no clearance yet"
 __device__ double order_value(unsigned long long k) {
   return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-struct LdsColumn {
-  double* p;   // element i at p[i * kThreads]
-  __device__ double& operator[](int i) { return p[i * kThreads]; }
-};
-
-__global__ void mtg_halfplane_init_kernel(HpParams P) {
-  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= P.B) return;
-  P.traj_word[b] = kNoFailure;
-  if (P.traj_clearance) reinterpret_cast<unsigned long long*>(P.traj_clearance)[b] = order_key(INFINITY);
 }
 
 // SHARED: one plane set for every lane (both strides 0) -- the set's address is a kernel argument, its loads are scalar and
@@ -62,31 +47,26 @@ __global__ void mtg_halfplane_init_kernel(HpParams P) {
 template <int NC, bool SHARED>
 __global__ __launch_bounds__(kThreads) void mtg_halfplane_seg_kernel(HpParams P) {
   __shared__ double lds[mtgh::roots_len(NC) * kThreads];
-  const long long total = P.B * P.K;
-  const long long idx = (long long)blockIdx.x * kThreads + threadIdx.x;
-  if (idx >= total) return;
-  const long long b = idx / P.K;
-  const int seg = (int)(idx - b * P.K);
-  const double T = P.times[b * P.ts_b + (long long)seg * P.ts_k];
-  const double* planes = SHARED ? P.planes : P.planes + b * P.ps_b + (long long)seg * P.ps_k;
-  LdsColumn roots{lds + threadIdx.x};
+  const mtgs::SegLane L = mtgs::seg_lane(P.s, (long long)blockIdx.x * kThreads + threadIdx.x);
+  if (!L.in_range) return;
+  const double* planes = SHARED ? P.planes : P.planes + L.b * P.ps_b + (long long)L.seg * P.ps_k;
+  mtgs::LdsColumn<kThreads> roots{lds + threadIdx.x};
   double clearance;
-  const int plane = mtgh::segment_check<NC, LdsColumn>(P.coeffs + idx * (long long)(P.D * P.N), P.N, P.D, T, planes, P.n_planes,
-                                                       roots, clearance);
-  if (P.seg_clearance) P.seg_clearance[idx] = clearance;
+  const int plane = mtgh::segment_check<NC, mtgs::LdsColumn<kThreads>>(L.c, P.s.N, P.s.D, L.T, planes, P.n_planes, roots, clearance);
+  if (P.seg_clearance) P.seg_clearance[L.idx] = clearance;
   if (P.traj_clearance && clearance == clearance)
-    atomicMin(reinterpret_cast<unsigned long long*>(P.traj_clearance) + b, order_key(clearance));
-  if (plane >= 0) atomicMin(P.traj_word + b, (seg << 8) | plane);
+    atomicMin(reinterpret_cast<unsigned long long*>(P.traj_clearance) + L.b, order_key(clearance));
+  if (plane >= 0) mtgs::report_failure(P.traj_word + L.b, L.seg, plane);
 }
 
 // FeasibilityBase::checkHalfPlaneFeasibility(const Trajectory&) (feasibility_base.cpp:109-117): the first segment that fails
 __global__ void mtg_halfplane_traj_kernel(HpParams P) {
   const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= P.B) return;
+  if (b >= P.s.B) return;
   const int w = P.traj_word[b];
-  const int plane = w & 0xff;
+  const int plane = mtgs::failure_code(w);
   P.traj_word[b] = w == kNoFailure ? 1 : 0;
-  if (P.first_segment) P.first_segment[b] = w == kNoFailure ? -1 : (w >> 8);
+  if (P.first_segment) P.first_segment[b] = w == kNoFailure ? -1 : mtgs::failure_segment(w);
   if (P.first_plane) P.first_plane[b] = (w == kNoFailure || plane == mtgh::kNoPlane) ? -1 : plane;
   if (P.traj_clearance) {
     const unsigned long long k = reinterpret_cast<unsigned long long*>(P.traj_clearance)[b];
@@ -94,18 +74,7 @@ __global__ void mtg_halfplane_traj_kernel(HpParams P) {
   }
 }
 
-template <int NC>
-void launch_seg(const HpParams& P, hipStream_t stream) {
-  const long long total = P.B * P.K;
-  const dim3 grid((unsigned)((total + kThreads - 1) / kThreads));
-  if (P.ps_b == 0 && P.ps_k == 0) hipLaunchKernelGGL((mtg_halfplane_seg_kernel<NC, true>), grid, dim3(kThreads), 0, stream, P);
-  else hipLaunchKernelGGL((mtg_halfplane_seg_kernel<NC, false>), grid, dim3(kThreads), 0, stream, P);
-}
-
 }  // namespace
-
-extern "C" int mtg_context_stream_device(mtg_context* ctx, void** stream, int* device);
-extern "C" int mtg_context_set_last_error(mtg_context* ctx, int code, const char* message);   // mtg_abi.hip
 
 extern "C" int mtg_check_half_plane_feasibility(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension,
                                                 int64_t batch, const double* coeffs, const double* times, int64_t times_stride_b,
@@ -125,27 +94,22 @@ extern "C" int mtg_check_half_plane_feasibility(mtg_context* ctx, int32_t n_coef
                                       "half-plane feasibility: 1 <= n_segments < 2^22, dimension >= 1, batch >= 0, times strides >= 1 that do "
                                       "not overlap ([B][K] or [K][B])");
   if (batch == 0) return MTG_OK;
-  void* stream = nullptr;
-  int device = 0;
-  int rc = mtg_context_stream_device(ctx, &stream, &device);
+  hipStream_t stream;
+  const int rc = mtgs::entry_stream(ctx, &stream);
   if (rc != MTG_OK) return rc;
-  if (hipSetDevice(device) != hipSuccess) return MTG_ERR_DEVICE;
   HpParams P;
-  P.coeffs = coeffs; P.times = times; P.planes = planes;
-  P.ts_b = times_stride_b; P.ts_k = times_stride_k; P.ps_b = planes_stride_b; P.ps_k = planes_stride_k;
+  P.s = {coeffs, times, times_stride_b, times_stride_k, batch, n_coeffs, n_segments, dimension};
+  P.planes = planes; P.ps_b = planes_stride_b; P.ps_k = planes_stride_k; P.n_planes = n_planes;
   P.traj_word = trajectory_feasible; P.first_segment = first_failing_segment; P.first_plane = first_failing_plane;
   P.seg_clearance = segment_clearance; P.traj_clearance = trajectory_clearance;
-  P.B = batch; P.N = n_coeffs; P.K = n_segments; P.D = dimension; P.n_planes = n_planes;
-  const dim3 per_traj((unsigned)((batch + 255) / 256));
-  hipLaunchKernelGGL(mtg_halfplane_init_kernel, per_traj, dim3(256), 0, (hipStream_t)stream, P);
-  // (an odd N, and N below 4, runs in the next even instantiation on zero-padded coefficients)
-  switch (mtgh::instance_of(n_coeffs)) {
-    case 4: launch_seg<4>(P, (hipStream_t)stream); break;
-    case 6: launch_seg<6>(P, (hipStream_t)stream); break;
-    case 8: launch_seg<8>(P, (hipStream_t)stream); break;
-    case 10: launch_seg<10>(P, (hipStream_t)stream); break;
-    default: launch_seg<12>(P, (hipStream_t)stream); break;
-  }
-  hipLaunchKernelGGL(mtg_halfplane_traj_kernel, per_traj, dim3(256), 0, (hipStream_t)stream, P);
+  const dim3 per_traj = mtgs::grid_for(batch, 256);
+  hipLaunchKernelGGL(mtgs::first_failure_init_kernel<unsigned long long>, per_traj, dim3(256), 0, stream, P.traj_word,
+                     reinterpret_cast<unsigned long long*>(P.traj_clearance), kKeyInfinity, P.s.B);
+  mtgs::with_instance<mtgh::kMinInstance>(n_coeffs, [&](auto nc) {
+    const dim3 grid = mtgs::grid_for(P.s.B * P.s.K, kThreads);
+    if (P.ps_b == 0 && P.ps_k == 0) hipLaunchKernelGGL((mtg_halfplane_seg_kernel<decltype(nc)::value, true>), grid, dim3(kThreads), 0, stream, P);
+    else hipLaunchKernelGGL((mtg_halfplane_seg_kernel<decltype(nc)::value, false>), grid, dim3(kThreads), 0, stream, P);
+  });
+  hipLaunchKernelGGL(mtg_halfplane_traj_kernel, per_traj, dim3(256), 0, stream, P);
   return hipGetLastError() == hipSuccess ? MTG_OK : MTG_ERR_DEVICE;
 }

@@ -83,16 +83,10 @@ extern "C" int mtg_check_half_plane_feasibility_host(int32_t n_coeffs, int32_t n
         const double* v = planes + b * planes_stride_b + k * planes_stride_k + 4 * h;
         if (!(std::fabs(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] - 1.0) <= 1e-9)) return MTG_ERR_INVALID_ARGUMENT;
       }
-#define MTG_HH(NC) run<NC>(n_coeffs, n_segments, dimension, batch, coeffs, times, times_stride_b, times_stride_k, planes, n_planes, \
-                           planes_stride_b, planes_stride_k, trajectory_feasible, first_failing_segment, first_failing_plane,        \
-                           segment_clearance, trajectory_clearance)
-  switch (mtgh::instance_of(n_coeffs)) {
-    case 4: MTG_HH(4); break;
-    case 6: MTG_HH(6); break;
-    case 8: MTG_HH(8); break;
-    case 10: MTG_HH(10); break;
-    default: MTG_HH(12); break;
-  }
-#undef MTG_HH
+  mtgs::with_instance<mtgh::kMinInstance>(n_coeffs, [&](auto nc) {
+    run<decltype(nc)::value>(n_coeffs, n_segments, dimension, batch, coeffs, times, times_stride_b, times_stride_k, planes, n_planes,
+                             planes_stride_b, planes_stride_k, trajectory_feasible, first_failing_segment, first_failing_plane,
+                             segment_clearance, trajectory_clearance);
+  });
   return MTG_OK;
 }

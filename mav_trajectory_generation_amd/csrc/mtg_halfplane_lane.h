@@ -29,7 +29,7 @@
 // Same code runs on the device (mtg_halfplane.hip) and on the host (mtg_halfplane_host.cpp).
 #pragma once
 
-#include "mtg_extrema_lane.h"
+#include "mtg_segment_lane.h"
 
 namespace mtgh {
 
@@ -41,17 +41,10 @@ constexpr int kNoPlane = 0xff;        // "infeasible before any plane was looked
 // what both entry points accept (include/mtg_hip.h)
 inline bool arguments_ok(int n_coeffs, int n_segments, int dimension, long long batch, long long ts_b, long long ts_k,
                          int n_planes, long long ps_b, long long ps_k) {
-  if (n_coeffs < 1 || n_coeffs > mtgx::kMaxCoeffs || n_segments < 1 || n_segments >= kMaxSegments || dimension < 1 ||
-      dimension > 32 || batch < 0)
-    return false;
-  if (ts_b < 1 || ts_k < 1) return false;
-  // [B][K] with rows at least K apart, or [K][B] with rows at least B apart: anything else aliases two segments' times
-  if (!(ts_b >= (long long)n_segments * ts_k || ts_k >= batch * ts_b)) return false;
-  if (n_planes < 1 || n_planes > kMaxPlanes || ps_b < 0 || ps_k < 0) return false;
-  return true;
+  return mtgs::shape_ok(n_coeffs, 1, n_segments, dimension, 32, batch, ts_b, ts_k) && n_segments < kMaxSegments &&
+         n_planes >= 1 && n_planes <= kMaxPlanes && ps_b >= 0 && ps_k >= 0;
 }
 
-constexpr int instance_of(int n_coeffs) { return n_coeffs <= kMinInstance ? kMinInstance : (n_coeffs + 1) & ~1; }
 constexpr int roots_len(int nc) { return 2 * (nc - 2); }   // the two buffers of real_roots_unit<nc - 1>
 
 // One segment against one plane set.  c = [D][N] coefficients (increasing powers), N <= NC; planes = P x (nx, ny, nz, offset);
@@ -64,10 +57,7 @@ MTGX_HD int segment_check(const double* c, int N, int D, double T, const double*
     return kNoPlane;
   }
   double p[3][NC];
-#pragma unroll
-  for (int d = 0; d < 3; ++d)
-#pragma unroll
-    for (int i = 0; i < NC; ++i) p[d][i] = i < N ? c[d * N + i] : 0.0;
+  mtgs::load_padded(c, N, D, p);
   double tpow[NC - 1];   // T^j
   tpow[0] = 1.0;
 #pragma unroll

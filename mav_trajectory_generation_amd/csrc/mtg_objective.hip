@@ -9,21 +9,17 @@
 // atomic maximum on the BIT PATTERN -- magnitudes are non-negative, so unsigned order is numeric order, and the result does not
 // depend on which lane arrives first; a NaN maximum (non-finite coefficients: mtg_objective_lane.h) is above every number in that
 // order and stays, whichever segment it comes from.  A lane per trajectory then forms the components (cost arithmetic: mtg_objective_lane.h).
-#include <hip/hip_runtime.h>
-
 #include <cmath>
 
-#include "../../include/mtg_hip.h"
 #include "mtg_objective_lane.h"
+#include "mtg_segment_kernel.h"
 
 namespace {
 
 constexpr int kThreads = 64;   // roots per lane: 30 doubles at N = 10 (15 KB per workgroup), 38 at N = 12 (19 KB)
 
 struct ObjParams {
-  const double* coeffs;   // [B][K][D][N]
-  const double* times;    // times[b*ts_b + k*ts_k]
-  long long ts_b, ts_k;
+  mtgs::SegShape s;
   unsigned long long* slots;   // [B][slot_stride]: bit patterns of the maxima so far; zero-filled before the search
   int slot_stride;
   const double* cost_trajectory;   // [B] or null (soft cost alone)
@@ -33,30 +29,19 @@ struct ObjParams {
   double* cost_soft;      // [B] or null
   double* maxima;         // [B][n] or null (may alias slots when slot_stride == n)
   double* violations;     // [B][n] or null
-  long long B;
-  int N, K, D;
   int time_cost_kind, use_soft;
   double time_penalty, weight, maximum_cost;
   mtgo::Constraints con;
 };
 
-struct LdsColumn {
-  double* p;   // element i at p[i * kThreads]
-  __device__ double& operator[](int i) { return p[i * kThreads]; }
-};
-
 template <int NC, int DC>
 __global__ __launch_bounds__(kThreads) void mtg_objective_seg_kernel(ObjParams P) {
   extern __shared__ double lds[];
-  const long long total = P.B * P.K;
-  const long long idx = (long long)blockIdx.x * kThreads + threadIdx.x;
-  if (idx >= total) return;
-  const long long b = idx / P.K;
-  const int seg = (int)(idx - b * P.K);
-  const double T = P.times[b * P.ts_b + (long long)seg * P.ts_k];
-  LdsColumn roots{lds + threadIdx.x};
-  unsigned long long* slot = P.slots + b * P.slot_stride;
-  mtgo::segment_maxima<NC, DC, LdsColumn>(P.coeffs + idx * (long long)(P.D * P.N), P.N, P.D, T, P.con, roots, [slot](int q, double m) {
+  const mtgs::SegLane L = mtgs::seg_lane(P.s, (long long)blockIdx.x * kThreads + threadIdx.x);
+  if (!L.in_range) return;
+  mtgs::LdsColumn<kThreads> roots{lds + threadIdx.x};
+  unsigned long long* slot = P.slots + L.b * P.slot_stride;
+  mtgo::segment_maxima<NC, DC, mtgs::LdsColumn<kThreads>>(L.c, P.s.N, P.s.D, L.T, P.con, roots, [slot](int q, double m) {
     atomicMax(slot + q, (unsigned long long)__double_as_longlong(m));
   });
 }
@@ -67,11 +52,11 @@ __global__ void mtg_objective_finish_kernel(ObjParams P) {
   // next to it (contracted, cost_trajectory + T * T * penalty became one fused operation and differed from it in the last bit)
 #pragma clang fp contract(off)
   const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= P.B) return;
+  if (b >= P.s.B) return;
   double total_time = 0.0;
   bool bad = P.tstatus && P.tstatus[b] != 0;
-  for (int k = 0; k < P.K; ++k) {   // computeTotalTrajectoryTime: in segment order
-    const double T = P.times[b * P.ts_b + (long long)k * P.ts_k];
+  for (int k = 0; k < P.s.K; ++k) {   // computeTotalTrajectoryTime: in segment order
+    const double T = P.s.times[b * P.s.ts_b + (long long)k * P.s.ts_k];
     bad = bad || !(T > 0.0);
     total_time += T;
   }
@@ -102,29 +87,21 @@ __global__ void mtg_objective_finish_kernel(ObjParams P) {
 }
 
 template <int NC, int DC>
-void launch_seg_nd(const ObjParams& P, hipStream_t stream) {
-  const long long total = P.B * P.K;
-  const size_t lds = (size_t)kThreads * mtgo::roots_len(NC) * sizeof(double);
-  hipLaunchKernelGGL((mtg_objective_seg_kernel<NC, DC>), dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), lds, stream, P);
-}
-template <int NC>
 void launch_seg(const ObjParams& P, hipStream_t stream) {
-  if (P.D <= 3) launch_seg_nd<NC, 3>(P, stream);
-  else launch_seg_nd<NC, 4>(P, stream);
+  const size_t lds = (size_t)kThreads * mtgo::roots_len(NC) * sizeof(double);
+  hipLaunchKernelGGL((mtg_objective_seg_kernel<NC, DC>), mtgs::grid_for(P.s.B * P.s.K, kThreads), dim3(kThreads), lds, stream, P);
 }
 
 // zero the slots, search, finish.  P.slots / P.slot_stride set by the caller.
 int run_stages(const ObjParams& P, hipStream_t stream) {
   if (P.con.n > 0) {
-    if (hipMemsetAsync(P.slots, 0, (size_t)P.B * P.slot_stride * sizeof(double), stream) != hipSuccess) return MTG_ERR_DEVICE;
-    // (an odd N runs in the next even instantiation on zero-padded coefficients)
-    if (P.N <= 4) launch_seg<4>(P, stream);
-    else if (P.N <= 6) launch_seg<6>(P, stream);
-    else if (P.N <= 8) launch_seg<8>(P, stream);
-    else if (P.N <= 10) launch_seg<10>(P, stream);
-    else launch_seg<12>(P, stream);
+    if (hipMemsetAsync(P.slots, 0, (size_t)P.s.B * P.slot_stride * sizeof(double), stream) != hipSuccess) return MTG_ERR_DEVICE;
+    mtgs::with_instance<4>(P.s.N, [&](auto nc) {
+      if (P.s.D <= 3) launch_seg<decltype(nc)::value, 3>(P, stream);
+      else launch_seg<decltype(nc)::value, 4>(P, stream);
+    });
   }
-  hipLaunchKernelGGL(mtg_objective_finish_kernel, dim3((unsigned)((P.B + 255) / 256)), dim3(256), 0, stream, P);
+  hipLaunchKernelGGL(mtg_objective_finish_kernel, mtgs::grid_for(P.s.B, 256), dim3(256), 0, stream, P);
   return hipGetLastError() == hipSuccess ? MTG_OK : MTG_ERR_DEVICE;
 }
 
@@ -135,8 +112,6 @@ void fill_params(ObjParams& P, const mtg_time_objective_params& par) {
 
 }  // namespace
 
-extern "C" int mtg_context_stream_device(mtg_context* ctx, void** stream, int* device);
-extern "C" int mtg_context_set_last_error(mtg_context* ctx, int code, const char* message);   // mtg_abi.hip
 extern "C" int mtg_plan_objective_solve(mtg_plan* plan, int64_t batch, const mtg_layout* layout, const double* times,
                                         const double* d_fixed, const double* d_free_in, double* coeffs, double** cost, double** slots,
                                         int32_t** tstatus);   // mtg_dispatch.hip
@@ -160,23 +135,20 @@ extern "C" int mtg_time_objective(mtg_plan* plan, int64_t batch, const mtg_layou
                                       "time objective: n_coeffs in [4,12], dimension <= 4, batch >= 0, times strides >= 1 that do not overlap, "
                                       "constraint derivatives in [1, N/2-1] with values > 0");
   if (batch == 0) return MTG_OK;
-  void* stream = nullptr;
-  int device = 0;
-  int rc = mtg_context_stream_device(ctx, &stream, &device);
+  hipStream_t stream;
+  int rc = mtgs::entry_stream(ctx, &stream);
   if (rc != MTG_OK) return rc;
   double* cost = nullptr;
   double* slots = nullptr;
   int32_t* tstatus = nullptr;
   rc = mtg_plan_objective_solve(plan, batch, layout, times, d_fixed, d_free_in, coeffs, &cost, &slots, &tstatus);
   if (rc != MTG_OK) return rc;
-  if (hipSetDevice(device) != hipSuccess) return MTG_ERR_DEVICE;
-  P.coeffs = coeffs; P.times = times; P.ts_b = layout->times_stride_b; P.ts_k = layout->times_stride_k;
+  P.s = {coeffs, times, layout->times_stride_b, layout->times_stride_k, batch, n, k, dim};
   P.slots = reinterpret_cast<unsigned long long*>(slots); P.slot_stride = mtgo::kMaxConstraints;
   P.cost_trajectory = cost; P.tstatus = tstatus;
   P.objective = objective; P.components = components; P.cost_soft = nullptr; P.maxima = maxima; P.violations = violations;
-  P.B = batch; P.N = n; P.K = k; P.D = dim;
   fill_params(P, *params);
-  return run_stages(P, (hipStream_t)stream);
+  return run_stages(P, stream);
 }
 
 extern "C" int mtg_magnitude_soft_cost(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
@@ -197,16 +169,13 @@ extern "C" int mtg_magnitude_soft_cost(mtg_context* ctx, int32_t n_coeffs, int32
   if (P.con.n > 0 && !maxima)
     return mtg_context_set_last_error(ctx, MTG_ERR_INVALID_ARGUMENT, "magnitude soft cost: maxima is required (the search reduces into it)");
   if (batch == 0) return MTG_OK;
-  void* stream = nullptr;
-  int device = 0;
-  const int rc = mtg_context_stream_device(ctx, &stream, &device);
+  hipStream_t stream;
+  const int rc = mtgs::entry_stream(ctx, &stream);
   if (rc != MTG_OK) return rc;
-  if (hipSetDevice(device) != hipSuccess) return MTG_ERR_DEVICE;
-  P.coeffs = coeffs; P.times = times; P.ts_b = times_stride_b; P.ts_k = times_stride_k;
+  P.s = {coeffs, times, times_stride_b, times_stride_k, batch, n_coeffs, n_segments, dimension};
   P.slots = reinterpret_cast<unsigned long long*>(maxima); P.slot_stride = P.con.n;   // finished in place: the bits ARE the doubles
   P.cost_trajectory = nullptr; P.tstatus = nullptr;
   P.objective = nullptr; P.components = nullptr; P.cost_soft = cost_soft; P.maxima = nullptr; P.violations = violations;
-  P.B = batch; P.N = n_coeffs; P.K = n_segments; P.D = dimension;
   fill_params(P, *params);
-  return run_stages(P, (hipStream_t)stream);
+  return run_stages(P, stream);
 }

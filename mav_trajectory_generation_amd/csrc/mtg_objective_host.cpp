@@ -82,20 +82,13 @@ extern "C" int mtg_magnitude_soft_cost_host(int32_t n_coeffs, int32_t n_segments
   if (mtg_objective_constraints(params, &con) != MTG_OK) return MTG_ERR_INVALID_ARGUMENT;
   if (!mtgo::arguments_ok(n_coeffs, n_segments, dimension, batch, times_stride_b, times_stride_k, con))
     return MTG_ERR_INVALID_ARGUMENT;
-#define MTG_OH(NC)                                                                                                          \
-  do {                                                                                                                      \
-    if (dimension <= 3) run<NC, 3>(n_coeffs, n_segments, dimension, batch, coeffs, times, times_stride_b, times_stride_k,   \
-                                   con, *params, cost_soft, maxima, violations);                                            \
-    else run<NC, 4>(n_coeffs, n_segments, dimension, batch, coeffs, times, times_stride_b, times_stride_k, con, *params,    \
-                    cost_soft, maxima, violations);                                                                         \
-  } while (0)
-  // (an odd N runs in the next even instantiation on zero-padded coefficients)
-  if (n_coeffs <= 4) MTG_OH(4);
-  else if (n_coeffs <= 6) MTG_OH(6);
-  else if (n_coeffs <= 8) MTG_OH(8);
-  else if (n_coeffs <= 10) MTG_OH(10);
-  else MTG_OH(12);
-#undef MTG_OH
+  mtgs::with_instance<4>(n_coeffs, [&](auto nc) {
+    constexpr int NC = decltype(nc)::value;
+    if (dimension <= 3) run<NC, 3>(n_coeffs, n_segments, dimension, batch, coeffs, times, times_stride_b, times_stride_k,
+                                   con, *params, cost_soft, maxima, violations);
+    else run<NC, 4>(n_coeffs, n_segments, dimension, batch, coeffs, times, times_stride_b, times_stride_k, con, *params,
+                    cost_soft, maxima, violations);
+  });
   return MTG_OK;
 }
 

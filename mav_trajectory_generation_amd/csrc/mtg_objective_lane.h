@@ -13,7 +13,7 @@
 // Same code runs on the device (mtg_objective.hip) and on the host (mtg_objective_host.cpp).
 #pragma once
 
-#include "mtg_extrema_lane.h"
+#include "mtg_segment_lane.h"
 
 namespace mtgo {
 
@@ -30,53 +30,25 @@ struct Constraints {   // ordered as the caller added them (addMaximumMagnitudeC
 // what the entry points accept (include/mtg_hip.h)
 inline bool arguments_ok(int n_coeffs, int n_segments, int dimension, long long batch, long long ts_b, long long ts_k,
                          const Constraints& c) {
-  if (n_coeffs < kMinCoeffs || n_coeffs > mtgx::kMaxCoeffs || n_segments < 1 || dimension < 1 || dimension > kMaxDimension || batch < 0)
-    return false;
-  if (ts_b < 1 || ts_k < 1) return false;
-  if (!(ts_b >= (long long)n_segments * ts_k || ts_k >= batch * ts_b)) return false;   // [B][K] or [K][B] without overlap
+  if (!mtgs::shape_ok(n_coeffs, kMinCoeffs, n_segments, dimension, kMaxDimension, batch, ts_b, ts_k)) return false;
   if (c.n < 0 || c.n > kMaxConstraints) return false;
   for (int q = 0; q < c.n; ++q)
     if (c.derivative[q] < 1 || c.derivative[q] > n_coeffs / 2 - 1 || !(c.value[q] > 0.0)) return false;
   return true;
 }
 
-// || p^(DER)(t) || over DC dimensions (Polynomial::evaluate: Horner over base(DER, i) c_i from the highest power down)
+// || p^(DER)(t) || over DC dimensions
 template <int NC, int DC, int DER>
 MTGX_HD double magnitude_at(const double (&p)[DC][NC], double t) {
-  double acc = 0.0;
-#pragma unroll
-  for (int d = 0; d < DC; ++d) {
-    double r = 0.0;
-#pragma unroll
-    for (int i = NC - 1; i >= DER; --i) r = fma(r, t, mtgx::falling_factorial(i, DER) * p[d][i]);
-    acc = fma(r, r, acc);
-  }
-  return sqrt(acc);
+  return mtgs::magnitude_at<NC, DC, DER, false>(p, nullptr, t);
 }
 
-// largest ||p^(DER)|| over [0, T]: start, interior critical points (real roots in tau = t / T of the convolved polynomial of
-// segment.cpp:96-115), end
+// largest ||p^(DER)|| over [0, T]: start, interior critical points, end
 template <int NC, int DC, int DER, class Roots>
 MTGX_HD double magnitude_max(const double (&p)[DC][NC], double T, Roots& roots) {
-  constexpr int NQ = NC - DER;
-  constexpr int L = 2 * NQ - 2;
+  constexpr int L = 2 * (NC - DER) - 2;
   double g[L];
-#pragma unroll
-  for (int j = 0; j < L; ++j) g[j] = 0.0;
-#pragma unroll
-  for (int d = 0; d < DC; ++d) {
-    double u[NQ];
-    double tp = 1.0;
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      u[i] = p[d][i + DER] * mtgx::falling_factorial(i + DER, DER) * tp;
-      tp *= T;
-    }
-#pragma unroll
-    for (int i = 0; i < NQ; ++i)
-#pragma unroll
-      for (int j = 0; j + 1 < NQ; ++j) g[i + j] = fma(u[i], (double)(j + 1) * u[j + 1], g[i + j]);
-  }
+  mtgs::magnitude_derivative<NC, DC, DER, false>(p, nullptr, T, g);
   int base = 0;
   const int cnt = mtgx::real_roots_unit<L, Roots>(g, roots, base);
   double best = fmax(magnitude_at<NC, DC, DER>(p, 0.0), magnitude_at<NC, DC, DER>(p, T));
@@ -110,10 +82,7 @@ MTGX_HD void search_order(const double (&p)[DC][NC], double T, const Constraints
 template <int NC, int DC, class Roots, class Emit>
 MTGX_HD void segment_maxima(const double* c, int N, int D, double T, const Constraints& con, Roots& roots, Emit&& emit) {
   double p[DC][NC];
-#pragma unroll
-  for (int d = 0; d < DC; ++d)
-#pragma unroll
-    for (int i = 0; i < NC; ++i) p[d][i] = (d < D && i < N) ? c[d * N + i] : 0.0;
+  mtgs::load_padded(c, N, D, p);
   search_order<NC, DC, 1, Roots>(p, T, con, roots, emit);
   search_order<NC, DC, 2, Roots>(p, T, con, roots, emit);
   search_order<NC, DC, 3, Roots>(p, T, con, roots, emit);
