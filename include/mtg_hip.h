@@ -416,6 +416,58 @@ int mtg_check_input_feasibility_host(int32_t n_coeffs, int32_t n_segments, int32
                                      int32_t* trajectory_result, int32_t* first_failing_segment,
                                      int32_t* segment_result, double* segment_bounds);
 
+/* ---- the cheap, conservative input check: batched recursive input-feasibility check ----------
+ * Replaces, for a batch, FeasibilityRecursive::checkInputFeasibility(const Segment&) with checkInputFeasibilityTrajectory
+ * (mav_trajectory_generation_ros/src/feasibility_recursive.cpp:42-297): Mueller's recursive test on single-axis
+ * extrema.  Per segment only the real roots of the acceleration, jerk and snap polynomials of x, y, z are needed
+ * (degree N - 3, N - 4, N - 5) instead of the analytic check's three magnitude searches.  Everything not named here is
+ * mtg_check_input_feasibility's: N in 5 .. 12, the times strides, the result codes, mtg_input_constraints (a NaN limit
+ * is absent; min_section_time_s is FeasibilityRecursive::Settings', default 0.05), the argument errors, device pointers,
+ * asynchronous on the context's stream: a caller swaps checkers by swapping the function name.
+ * Per segment: the value FeasibilityRecursive::checkInputFeasibility(const Segment&) returns; per trajectory: the result
+ * of the first segment (in segment order) that is not feasible; dimension other than 3 or 4: MTG_INPUT_INDETERMINABLE
+ * everywhere.  Faithful to the reference, quirks included:
+ *   - a section shorter than min_section_time_s is indeterminable before anything else is looked at: a whole segment
+ *     with T < min_section_time_s is MTG_INPUT_INDETERMINABLE even with no limit set;
+ *   - order inside a section [t1, t2]: (1) thrust at both ends, low before high; (2) velocity at both ends; (3) per-axis
+ *     velocity extrema in axis order, a single axis above v_max fails at once; (4) per-axis thrust extrema, a single axis
+ *     above f_max fails at once, a sign change gives a zero lower-bound term; (5) jerk extrema; (6) f_upper < f_min:
+ *     thrust low; (7) f_lower > f_max: thrust high; (8) any bound beyond its limit: split at (t1 + t2) / 2, first half
+ *     first, and return the first result that is not feasible;
+ *   - a lower-bound thrust^2 <= 1e-6 makes the roll/pitch bound DBL_MAX;
+ *   - all comparisons are strict;
+ *   - MTG_INPUT_INFEASIBLE_ROLL_PITCH_RATES is never returned;
+ *   - yaw rate, then yaw acceleration, are checked over the whole segment only after the recursion returned feasible,
+ *     and only for dimension 4;
+ *   - Polynomial::getRoots returning false does not occur: the real roots in [0, T] are isolated directly;
+ *   - one guard of our own, as in the analytic check: depth 62 ends the walk as MTG_INPUT_INDETERMINABLE (with
+ *     min_section_time_s = 0 the reference recurses without end).
+ *   segment_bounds    out optional [batch][K][6], 16-byte aligned: the bounds of the whole-segment section [0, T] --
+ *                         f_lower_bound, f_upper_bound, v_upper_bound, the roll/pitch bound -- then |yaw rate| maximum and
+ *                         |yaw acceleration| maximum; NaN where the quantity's limit is absent (the thrust bounds are
+ *                         computed when any of f_min, f_max, omega_xy_max is set).  A value is computed whenever its
+ *                         limit is set, whatever the verdict and even where T < min_section_time_s: the reference
+ *                         returns early here.
+ *   segment_sections  out optional [batch][K]: the sections the walk examined, i.e. the calls of recursiveFeasibility
+ *                         that got past the minimum-section-time test: 1 for a segment decided at the top, 0 if
+ *                         T < min_section_time_s.  A measure of how hard a segment was.
+ * A verdict can differ from the reference's only where a bound lies within rounding of its limit or a root's time
+ * within rounding of a section's end.                                                                            */
+int mtg_check_input_feasibility_recursive(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension,
+                                          int64_t batch, const double* coeffs, const double* times,
+                                          int64_t times_stride_b, int64_t times_stride_k,
+                                          const mtg_input_constraints* constraints, int32_t* trajectory_result,
+                                          int32_t* first_failing_segment, int32_t* segment_result, double* segment_bounds,
+                                          int32_t* segment_sections);
+/* The same check with HOST pointers on the library's host build of the same code, synchronous; needs no context and
+ * no device.  segment_bounds needs no alignment here.                                                             */
+int mtg_check_input_feasibility_recursive_host(int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                                               const double* coeffs, const double* times, int64_t times_stride_b,
+                                               int64_t times_stride_k, const mtg_input_constraints* constraints,
+                                               int32_t* trajectory_result, int32_t* first_failing_segment,
+                                               int32_t* segment_result, double* segment_bounds,
+                                               int32_t* segment_sections);
+
 /* ---- next to the input check: batched half-plane / flight-corridor feasibility check ------------
  * Replaces, for a batch, FeasibilityBase::checkHalfPlaneFeasibility(const Segment&) / (const Trajectory&) over
  * half_plane_constraints_ (mav_trajectory_generation_ros/src/feasibility_base.cpp:109-154) and the HalfPlane helpers

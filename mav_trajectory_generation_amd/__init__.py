@@ -8,6 +8,7 @@ from .core import Context, Plan, MtgError, MultiSolve, solve_linear_batch, libra
 from .core import minmax_magnitude, scale_segment_times_to_meet_constraints, pack_multi_items, PackedMultiSolve  # noqa: F401
 from .core import InputConstraints, InputFeasibilityResult, check_input_feasibility, check_input_feasibility_host  # noqa: F401
 from .core import get_input_feasibility_result_name  # noqa: F401
+from .core import check_input_feasibility_recursive, check_input_feasibility_recursive_host  # noqa: F401
 from .core import half_planes, bounding_box_half_planes, check_half_plane_feasibility, check_half_plane_feasibility_host  # noqa: F401
 from .core import HalfPlaneFeasibilityResult  # noqa: F401
 from .workload import ends_full_masks, random_waypoint_batch  # noqa: F401

@@ -130,6 +130,13 @@ EXPORTS = {
     "mtg_check_input_feasibility_host": (ctypes.c_int, [
         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
         ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p]),
+    "mtg_check_input_feasibility_recursive": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
+        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        c_double_p, ctypes.c_void_p]),
+    "mtg_check_input_feasibility_recursive_host": (ctypes.c_int, [
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
+        ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p]),
     "mtg_check_half_plane_feasibility": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
         ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,

@@ -354,6 +354,66 @@ def check_input_feasibility_host(coeffs, times, constraints: InputConstraints, t
     return traj, first, seg, bounds
 
 
+def check_input_feasibility_recursive(ctx: "Context", coeffs, times, constraints: InputConstraints, times_layout: str = "aos",
+                                      want_segments: bool = True, want_bounds: bool = True, want_sections: bool = False):
+    """Batched FeasibilityRecursive::checkInputFeasibilityTrajectory (Mueller's recursive test on single-axis extrema, the cheap
+    and conservative checker): the arguments of check_input_feasibility -> (trajectory_result [B] int32, first_failing_segment
+    [B] int32 (-1: none), segment_result [B][K] int32 or None, segment_bounds [B][K][6] or None: f_lower_bound, f_upper_bound,
+    v_upper_bound and roll/pitch bound of the whole-segment section [0, T], |yaw rate| max, |yaw acceleration| max; NaN where
+    not computed, segment_sections [B][K] int32 or None: the sections the walk examined).  constraints.min_section_time_s is
+    FeasibilityRecursive::Settings' value.  Result codes: InputFeasibilityResult."""
+    import torch
+    bsz, k, dim, n = coeffs.shape
+    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
+    dev = coeffs.device
+    traj = torch.empty((bsz,), dtype=torch.int32, device=dev)
+    first = torch.empty((bsz,), dtype=torch.int32, device=dev)
+    seg = torch.empty((bsz, k), dtype=torch.int32, device=dev) if want_segments else None
+    bounds = torch.empty((bsz, k, 6), dtype=torch.float64, device=dev) if want_bounds else None
+    sections = torch.empty((bsz, k), dtype=torch.int32, device=dev) if want_sections else None
+    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
+    c = constraints.to_c()
+    cur = ctx._enter()
+    rc = ctx.lib.mtg_check_input_feasibility_recursive(
+        ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()), ctypes.c_void_p(times.data_ptr()), sb, sk, ctypes.byref(c),
+        ctypes.c_void_p(traj.data_ptr()), ctypes.c_void_p(first.data_ptr()),
+        ctypes.c_void_p(seg.data_ptr()) if seg is not None else None,
+        ctypes.c_void_p(bounds.data_ptr()) if bounds is not None else None,
+        ctypes.c_void_p(sections.data_ptr()) if sections is not None else None)
+    ctx._leave(cur)
+    _check(ctx.lib, rc, ctx.handle)
+    return traj, first, seg, bounds, sections
+
+
+def check_input_feasibility_recursive_host(coeffs, times, constraints: InputConstraints, times_layout: str = "aos"):
+    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
+    [B][K][D][N] or one trajectory [K][D][N]; returns numpy (trajectory_result, first_failing_segment, segment_result,
+    segment_bounds, segment_sections), shaped as the device form's (without the batch axis for one trajectory)."""
+    lib = L.load()
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    single = coeffs.ndim == 3
+    if single:
+        coeffs, times = coeffs[None], times[None]
+    bsz, k, dim, n = coeffs.shape
+    if times.size != bsz * k:
+        raise MtgError(-1, "times must hold one value per segment")
+    traj = np.empty((bsz,), dtype=np.int32)
+    first = np.empty((bsz,), dtype=np.int32)
+    seg = np.empty((bsz, k), dtype=np.int32)
+    bounds = np.empty((bsz, k, 6), dtype=np.float64)
+    sections = np.empty((bsz, k), dtype=np.int32)
+    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
+    c = constraints.to_c()
+    rc = lib.mtg_check_input_feasibility_recursive_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk,
+                                                        ctypes.byref(c), traj.ctypes.data, first.ctypes.data, seg.ctypes.data,
+                                                        bounds.ctypes.data, sections.ctypes.data)
+    _check(lib, rc)
+    if single:
+        return traj[0], first[0], seg[0], bounds[0], sections[0]
+    return traj, first, seg, bounds, sections
+
+
 def half_planes(points, normals) -> np.ndarray:
     """HalfPlane(point, normal) for n planes: points [n][3], normals [n][3] (any length > 0) -> [n][4] rows (unit normal,
     offset = point . normal), the plane format of check_half_plane_feasibility.  A zero normal raises."""

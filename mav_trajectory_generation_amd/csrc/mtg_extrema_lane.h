@@ -28,6 +28,7 @@
 
 #include <cfloat>
 #include <cmath>
+#include <type_traits>
 
 #if defined(__HIPCC__)
 #define MTGX_HD __host__ __device__ inline
@@ -223,12 +224,16 @@ struct Share { int part_begin, part_end, nparts; };   // nparts <= 4
 // with the coefficients above the level's degree zero (~1.6x the FMAs, 1/15 of the code) -- built to test whether instruction
 // fetch bounds small launches (a lone wave runs at ~12 cycles per instruction): it does not, the rolled form is 15-20 % SLOWER
 // (profiles/r04f_extrema_variants.jsonl); kept selectable (measurement knob), the per-level bodies are the default.
-template <int M, int K, class Roots, bool ROLLED = false>
+// TIGHT: the last TIGHT levels are refined to kRootTol (1: only g itself); Sink: sees every level's roots before the next level
+// overwrites them (sink->template level<K>(roots, offset, count)) -- the roots of g's derivatives come with a search of g
+// (mtg_recursive_lane.h: the jerk and snap roots with the acceleration polynomial's).  The per-level bodies only.
+struct NoSink {};
+template <int M, int K, class Roots, bool ROLLED = false, int TIGHT = 1, class Sink = NoSink>
 struct Level {
-  static MTGX_HD void run(const double* g, double* a, Roots& roots, int& cnt, const Share& sh, int kr = K) {
+  static MTGX_HD void run(const double* g, double* a, Roots& roots, int& cnt, const Share& sh, int kr = K, Sink* sink = nullptr) {
     constexpr int KH = ROLLED ? M : K;
     const int SRC = ROLLED ? ((kr - 1) & 1) * M : ((K - 1) & 1) * M, DST = ROLLED ? (kr & 1) * M : (K & 1) * M;
-    const double tol = (ROLLED ? kr < M : K < M) ? kPartitionTol : kRootTol;
+    const double tol = (ROLLED ? kr < M : K + TIGHT <= M) ? kPartitionTol : kRootTol;
     double anorm = 0.0;
 #pragma unroll
     for (int j = 0; j <= KH; ++j) anorm += fabs(a[j]);
@@ -297,6 +302,7 @@ struct Level {
     }
     const int cnt_new = rank;
     cnt = cnt_new;
+    if constexpr (!ROLLED && !std::is_same<Sink, NoSink>::value) sink->template level<K>(roots, DST, cnt_new);
     if constexpr (ROLLED) {
       // integrate once (run-time level kr): a'_j = a_(j-1) s / j, s = M - kr; the entries above the new degree stay zero
       if (kr < M) {
@@ -312,15 +318,15 @@ struct Level {
 #pragma unroll
       for (int j = K + 1; j >= 1; --j) a[j] = a[j - 1] * ((double)s / (double)j);
       a[0] = g[s - 1];
-      Level<M, K + 1, Roots>::run(g, a, roots, cnt, sh);
+      Level<M, K + 1, Roots, false, TIGHT, Sink>::run(g, a, roots, cnt, sh, K + 1, sink);
     }
   }
 };
 
 // Real roots in [0, 1] of g(tau) = sum_j g[j] tau^j, j < L; ascending.  L >= 2.  `roots` holds 2 * (L - 1) elements (two
 // buffers the levels alternate between); returns the count and, in `base`, the offset of the buffer that holds the result.
-template <int L, class Roots, bool ROLLED = false>
-MTGX_HD int real_roots_unit(const double* g, Roots& roots, int& base, const Share& sh = Share{0, 1, 1}) {
+template <int L, class Roots, bool ROLLED = false, int TIGHT = 1, class Sink = NoSink>
+MTGX_HD int real_roots_unit(const double* g, Roots& roots, int& base, const Share& sh = Share{0, 1, 1}, Sink* sink = nullptr) {
   constexpr int M = L - 1;   // degree
   static_assert(M <= 31, "interval bit mask");
   double a[L];
@@ -332,7 +338,7 @@ MTGX_HD int real_roots_unit(const double* g, Roots& roots, int& base, const Shar
   if constexpr (ROLLED) {
     for (int kr = 1; kr <= M; ++kr) Level<M, 1, Roots, true>::run(g, a, roots, cnt, sh, kr);
   } else {
-    Level<M, 1, Roots>::run(g, a, roots, cnt, sh);
+    Level<M, 1, Roots, false, TIGHT, Sink>::run(g, a, roots, cnt, sh, 1, sink);
   }
   base = (M & 1) * M;
   return cnt;
