@@ -65,6 +65,48 @@ class TrajectoryBatch {
     return true;
   }
 
+  // Per-trajectory SIGNED extrema of every axis (Polynomial::computeMinMax over all segments, mtg_minmax_axes): minima and
+  // maxima have size() * D() entries, axis fastest; Extremum = (segment-local time, value, segment index).
+  bool computeAxisMinMax(int derivative, std::vector<Extremum>* minima, std::vector<Extremum>* maxima) {
+    CHECK_NOTNULL(minima);
+    CHECK_NOTNULL(maxima);
+    if (derivative < 0 || derivative > 4 || N_ - derivative - 1 < 0 || D_ > 8) return false;   // polynomial.cpp:70-73
+    const size_t rows = (size_t)B_ * D_;
+    double* seg = (double*)dmalloc(sizeof(double) * 4 * rows * K_);
+    double* traj = (double*)dmalloc(sizeof(double) * 4 * rows);
+    int32_t* idx = (int32_t*)dmalloc(sizeof(int32_t) * 2 * rows);
+    check(mtg_minmax_axes(ctx(), N_, K_, D_, B_, coeffs_, times_, K_, 1, derivative, 1, seg, traj, idx));
+    std::vector<double> h(4 * rows);
+    std::vector<int32_t> hi(2 * rows);
+    check(mtg_copy_to_host(ctx(), h.data(), traj, sizeof(double) * h.size()));
+    check(mtg_copy_to_host(ctx(), hi.data(), idx, sizeof(int32_t) * hi.size()));
+    mtg_device_free(ctx(), seg);
+    mtg_device_free(ctx(), traj);
+    mtg_device_free(ctx(), idx);
+    minima->resize(rows);
+    maxima->resize(rows);
+    for (size_t r = 0; r < rows; ++r) {
+      (*minima)[r] = Extremum(h[4 * r + 0], h[4 * r + 1], hi[2 * r + 0]);
+      (*maxima)[r] = Extremum(h[4 * r + 2], h[4 * r + 3], hi[2 * r + 1]);
+    }
+    return true;
+  }
+
+  // Axis-aligned bounding box of every trajectory's position: lo and hi have size() * D() entries, axis fastest.
+  bool boundingBoxes(std::vector<double>* lo, std::vector<double>* hi) {
+    CHECK_NOTNULL(lo);
+    CHECK_NOTNULL(hi);
+    std::vector<Extremum> mn, mx;
+    if (!computeAxisMinMax(derivative_order::POSITION, &mn, &mx)) return false;
+    lo->resize(mn.size());
+    hi->resize(mx.size());
+    for (size_t r = 0; r < mn.size(); ++r) {
+      (*lo)[r] = mn[r].value;
+      (*hi)[r] = mx[r].value;
+    }
+    return true;
+  }
+
   bool computeMaxVelocityAndAcceleration(std::vector<double>* v_max, std::vector<double>* a_max) {
     CHECK_NOTNULL(v_max);
     CHECK_NOTNULL(a_max);

@@ -338,6 +338,40 @@ int mtg_minmax_magnitude(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments,
                          int32_t derivative, uint32_t dimension_mask, double* segment_minmax,
                          double* trajectory_minmax, int32_t* trajectory_segment_idx);
 
+/* Per-axis extrema: the SIGNED minimum and maximum of single axes.  Replaces, for a batch, Polynomial::computeMinMax(0, T,
+ * q, &min, &max) -> selectMinMaxFromCandidates (src/polynomial.cpp:102-143) for every (trajectory, segment, axis) and
+ * every order q = derivative_first .. derivative_first + n_derivatives - 1 (0 = position .. 4 = snap), with ONE root
+ * search per axis: the derivative chain that isolates the roots of p^(derivative_first + 1) passes through the critical
+ * points of every higher order.
+ * The rule: the candidates of order q are 0, then T, then the real roots of p^(q+1) in [0, T] in ascending order; the
+ * running pair starts at (0, DBL_MAX) / (0, -DBL_MAX); both comparisons are strict, so the first candidate wins a tie and a
+ * constant derivative reports t = 0 twice.  Values are Polynomial::evaluate's Horner form.  The roots are isolated directly
+ * instead of running Jenkins-Traub, as in mtg_minmax_magnitude: same values; extremum TIMES agree only where the root is
+ * well conditioned.
+ * One departure from the reference: if any candidate value of a (segment, axis, order) is NaN its row is (0, NaN, 0, NaN)
+ * -- not the DBL_MAX / lowest sentinels, which a bounding-box caller would read as an empty box; in the per-trajectory
+ * reduction a NaN row wins and the first such segment is reported.  No other row differs.
+ *   n_coeffs 2..12, n_segments >= 1, dimension 1..8, batch >= 0; times[b * times_stride_b + k * times_stride_k] as in
+ *   mtg_minmax_magnitude; derivative_first >= 0, n_derivatives >= 1, last order <= min(4, n_coeffs - 1)
+ *   (polynomial.cpp:70-73)
+ *   segment_minmax    out [batch][K][D][n_derivatives][4] = (t_min, v_min, t_max, v_max), times relative to the segment
+ *                         start; required, 16-byte aligned on the device
+ *   trajectory_minmax out optional [batch][D][n_derivatives][4]: per (axis, order) the first segment with the strictly
+ *                         smallest / largest value, that segment's time and value
+ *   trajectory_segment_idx out optional [batch][D][n_derivatives][2] = (segment of the minimum, of the maximum); read only
+ *                         together with trajectory_minmax
+ * Argument errors return MTG_ERR_INVALID_ARGUMENT with nothing enqueued; batch == 0 returns before anything is enqueued.
+ * Device pointers; asynchronous on the context's stream; kernel launches only (capturable).                          */
+int mtg_minmax_axes(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                    const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                    int32_t derivative_first, int32_t n_derivatives, double* segment_minmax,
+                    double* trajectory_minmax, int32_t* trajectory_segment_idx);
+/* The same on host pointers through the library's host build of the same lane code: synchronous, no context, no device. */
+int mtg_minmax_axes_host(int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch, const double* coeffs,
+                         const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                         int32_t derivative_first, int32_t n_derivatives, double* segment_minmax,
+                         double* trajectory_minmax, int32_t* trajectory_segment_idx);
+
 /* Replaces, for a batch, Trajectory::scaleSegmentTimesToMeetConstraints(v_max, a_max) (src/trajectory.cpp:385-429)
  * on top of computeMaxVelocityAndAcceleration (:343-361): `max_iterations` rounds of { maximum |velocity| and
  * |acceleration| over all dimensions; if either exceeds its bound by more than 1e-3 relative, stretch every

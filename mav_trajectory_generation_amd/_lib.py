@@ -117,6 +117,12 @@ EXPORTS = {
     "mtg_minmax_magnitude": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                             c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                             ctypes.c_uint32, c_double_p, c_double_p, ctypes.c_void_p]),
+    "mtg_minmax_axes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                       c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                       c_double_p, c_double_p, ctypes.c_void_p]),
+    "mtg_minmax_axes_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p,
+                                            c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                            c_double_p, c_double_p, ctypes.c_void_p]),
     "mtg_scale_segment_times_to_meet_constraints": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
         ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, c_double_p, c_double_p,

@@ -204,6 +204,78 @@ def minmax_magnitude(ctx: "Context", coeffs, times, derivative: int, dimensions:
     return seg, traj, idx
 
 
+class AxisMinMax(NamedTuple):
+    """segment [B][K][D][n][4], trajectory [B][D][n][4] or None, trajectory_segment_idx [B][D][n][2] int32 or None; the four
+    columns are (t_min, v_min, t_max, v_max) with segment-local times, n the orders asked for."""
+    segment: object
+    trajectory: object
+    trajectory_segment_idx: object
+
+
+def minmax_axes(ctx: "Context", coeffs, times, derivative_first: int = 0, n_derivatives: int = 1, times_layout: str = "aos",
+                want_trajectory: bool = True) -> AxisMinMax:
+    """Batched Polynomial::computeMinMax: the signed minimum and maximum of every axis over every segment, for the orders
+    derivative_first .. derivative_first + n_derivatives - 1 (0 = position .. 4 = snap) from one root search per axis.  coeffs
+    [B][K][D][N], times ([B][K] 'aos' / [K][B] 'soa') CUDA float64 tensors.  A row with a NaN candidate is (0, NaN, 0, NaN)."""
+    import torch
+    bsz, k, dim, n = coeffs.shape
+    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
+    nd = int(n_derivatives)
+    if nd < 1 or nd > 5:
+        raise MtgError(-1, "n_derivatives must be in [1, 5]")
+    dev = coeffs.device
+    seg = torch.empty((bsz, k, dim, nd, 4), dtype=torch.float64, device=dev)
+    traj = torch.empty((bsz, dim, nd, 4), dtype=torch.float64, device=dev) if want_trajectory else None
+    idx = torch.empty((bsz, dim, nd, 2), dtype=torch.int32, device=dev) if want_trajectory else None
+    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
+    cur = ctx._enter()
+    rc = ctx.lib.mtg_minmax_axes(ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()), ctypes.c_void_p(times.data_ptr()),
+                                 sb, sk, int(derivative_first), nd, ctypes.c_void_p(seg.data_ptr()),
+                                 ctypes.c_void_p(traj.data_ptr()) if traj is not None else None,
+                                 ctypes.c_void_p(idx.data_ptr()) if idx is not None else None)
+    ctx._leave(cur)
+    _check(ctx.lib, rc, ctx.handle)
+    return AxisMinMax(seg, traj, idx)
+
+
+def minmax_axes_host(coeffs, times, derivative_first: int = 0, n_derivatives: int = 1, times_layout: str = "aos",
+                     want_trajectory: bool = True) -> AxisMinMax:
+    """The same on numpy arrays through the library's host build of the same code (no context, no device): coeffs
+    [B][K][D][N] or one trajectory [K][D][N] (then the results come without the batch axis)."""
+    lib = L.load()
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    single = coeffs.ndim == 3
+    if single:
+        coeffs, times = coeffs[None], times[None]
+    bsz, k, dim, n = coeffs.shape
+    if times.size != bsz * k:
+        raise MtgError(-1, "times must hold one value per segment")
+    nd = int(n_derivatives)
+    if nd < 1 or nd > 5:
+        raise MtgError(-1, "n_derivatives must be in [1, 5]")
+    seg = np.empty((bsz, k, dim, nd, 4), dtype=np.float64)
+    traj = np.empty((bsz, dim, nd, 4), dtype=np.float64) if want_trajectory else None
+    idx = np.empty((bsz, dim, nd, 2), dtype=np.int32) if want_trajectory else None
+    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
+    rc = lib.mtg_minmax_axes_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk, int(derivative_first), nd,
+                                  seg.ctypes.data, traj.ctypes.data if traj is not None else None,
+                                  idx.ctypes.data if idx is not None else None)
+    _check(lib, rc)
+    res = AxisMinMax(seg, traj, idx)
+    return AxisMinMax(*[a if a is None else a[0] for a in res]) if single else res
+
+
+def bounding_boxes(ctx: "Context", coeffs, times, times_layout: str = "aos", margin: float = 0.0):
+    """Axis-aligned bounding boxes of position from one minmax_axes call of order 0: (segment_lo_hi [B][K][2][D],
+    trajectory_lo_hi [B][2][D]), lo - margin / hi + margin."""
+    import torch
+    r = minmax_axes(ctx, coeffs, times, 0, 1, times_layout, True)
+    seg = torch.stack([r.segment[:, :, :, 0, 1] - margin, r.segment[:, :, :, 0, 3] + margin], dim=2)
+    traj = torch.stack([r.trajectory[:, :, 0, 1] - margin, r.trajectory[:, :, 0, 3] + margin], dim=1)
+    return seg, traj
+
+
 def scale_segment_times_to_meet_constraints(ctx: "Context", coeffs, times, v_max: float, a_max: float,
                                             max_iterations: int = 2, times_layout: str = "aos", workspace=None):
     """Batched Trajectory::scaleSegmentTimesToMeetConstraints, IN PLACE on coeffs [B][K][D][N] and times.
