@@ -3,10 +3,12 @@
 // (include/mtg_hip.h): evaluateRange / sampleTrajectoryInRange -> sample(), computeMinMaxMagnitude,
 // computeMaxVelocityAndAcceleration, scaleSegmentTimesToMeetConstraints (src/trajectory.cpp:81-141, :190-227,
 // :343-361, :385-429), and softConstraintCost -- the soft-constraint term of the time optimisers' objective
-// (PolynomialOptimizationNonLinear<N>::evaluateMaximumMagnitudeAsSoftConstraint).  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
+// (PolynomialOptimizationNonLinear<N>::evaluateMaximumMagnitudeAsSoftConstraint), and checkObstacleClearance -- clearance from a set
+// of spheres, what a caller of the reference loops offsetTrajectory + computeMinMaxMagnitude for.  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
 // The single-trajectory functions stay on the host (trajectory.h); this class is for B >> 1.
 #ifndef MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
 #define MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
+#include <cmath>
 #include <cstdint>
 #include <utility>
 #include <vector>
@@ -155,6 +157,43 @@ class TrajectoryBatch {
     return true;
   }
 
+  // Clearance of every trajectory from a set of spheres (mtg_check_obstacle_clearance): obstacles = M x (cx, cy, cz, r), shared by
+  // all trajectories; inflation = the vehicle's radius.  feasible[b]: min over [0, T] of ||p(t) - c|| - r - inflation > 0 for every
+  // sphere and segment; first_segment / first_obstacle: the first failing segment and its smallest failing sphere (-1: none);
+  // clearance[b]: the minimum itself (NaN wins).  The outputs are optional.  false: no or more than 4096 spheres, D not 3 or 4, more
+  // than 2^19 - 1 segments, a negative or non-finite inflation.  Returns true when the check ran, whatever the verdicts.
+  bool checkObstacleClearance(const std::vector<double>& obstacles, double inflation, std::vector<char>* feasible,
+                              std::vector<int>* first_segment = nullptr, std::vector<int>* first_obstacle = nullptr,
+                              std::vector<double>* clearance = nullptr) {
+    const size_t m = obstacles.size() / 4;
+    if (obstacles.size() % 4 != 0 || m < 1 || m > 4096 || !(D_ == 3 || D_ == 4) || K_ >= (1 << 19)) return false;
+    if (!(inflation >= 0.0) || inflation > 1.7976931348623157e308) return false;
+    double* d_obs = (double*)dmalloc(sizeof(double) * obstacles.size());
+    check(mtg_copy_to_device(ctx(), d_obs, obstacles.data(), sizeof(double) * obstacles.size()));
+    int32_t* d_int = (int32_t*)dmalloc(sizeof(int32_t) * 3 * B_);
+    double* d_clear = (double*)dmalloc(sizeof(double) * B_);
+    check(mtg_check_obstacle_clearance(ctx(), N_, K_, D_, B_, coeffs_, times_, K_, 1, d_obs, (int32_t)m, 0, inflation, d_int, d_int + B_,
+                                       d_int + 2 * B_, nullptr, nullptr, nullptr, d_clear));
+    std::vector<int32_t> h(3 * B_);
+    check(mtg_copy_to_host(ctx(), h.data(), d_int, sizeof(int32_t) * h.size()));
+    if (clearance) {
+      clearance->resize(B_);
+      check(mtg_copy_to_host(ctx(), clearance->data(), d_clear, sizeof(double) * B_));
+    }
+    mtg_device_free(ctx(), d_obs);
+    mtg_device_free(ctx(), d_int);
+    mtg_device_free(ctx(), d_clear);
+    if (feasible) feasible->resize(B_);
+    if (first_segment) first_segment->resize(B_);
+    if (first_obstacle) first_obstacle->resize(B_);
+    for (int64_t b = 0; b < B_; ++b) {
+      if (feasible) (*feasible)[b] = (char)(h[b] != 0);
+      if (first_segment) (*first_segment)[b] = h[B_ + b];
+      if (first_obstacle) (*first_obstacle)[b] = h[2 * B_ + b];
+    }
+    return true;
+  }
+
   // In place on the device copy; returns true when every trajectory ended within range.
   bool scaleSegmentTimesToMeetConstraints(double v_max, double a_max, std::vector<char>* within_range = nullptr,
                                           std::vector<double>* scaling = nullptr) {
@@ -265,6 +304,41 @@ class TrajectoryBatch {
   double* coeffs_ = nullptr;   // device [B][K][D][N]
   double* times_ = nullptr;    // device [B][K]
 };
+
+// One trajectory against a set of spheres on the HOST (mtg_check_obstacle_clearance_host: no device, no context).  The mtg prefix
+// says that this is an addition of this library: the reference has no such function, its callers loop
+// Trajectory::offsetTrajectory(-centre) + computeMinMaxMagnitude(POSITION, {0, 1, 2}) over the obstacles.  obstacles = M x (cx, cy,
+// cz, r).  Returns the verdict; first_segment / first_obstacle (-1: none) and clearance (the minimum of ||p(t) - c|| - r - inflation
+// over the trajectory, NaN wins) are optional.  Arguments the check refuses (no spheres, D not 3 or 4, a negative or non-finite radius
+// or inflation): false, with first_segment = first_obstacle = -1 and clearance NaN.
+inline bool mtgCheckObstacleClearance(const Trajectory& trajectory, const std::vector<double>& obstacles, double inflation = 0.0,
+                                      int* first_segment = nullptr, int* first_obstacle = nullptr, double* clearance = nullptr) {
+  const int n = trajectory.N(), k = trajectory.K(), dim = trajectory.D();
+  std::vector<double> c((size_t)k * dim * n), t((size_t)k);
+  for (int s = 0; s < k; ++s) {
+    const Segment& seg = trajectory.segments()[s];
+    t[s] = seg.getTime();
+    for (int d = 0; d < dim; ++d) {
+      const Eigen::VectorXd v = seg[d].getCoefficients();
+      for (int i = 0; i < n; ++i) c[((size_t)s * dim + d) * n + i] = v[i];
+    }
+  }
+  int32_t feasible = 0, fseg = -1, fobs = -1;
+  double lowest = 0.0;
+  const int rc = obstacles.size() % 4 != 0 ? MTG_ERR_INVALID_ARGUMENT
+                                            : mtg_check_obstacle_clearance_host(n, k, dim, 1, c.data(), t.data(), k, 1, obstacles.data(),
+                                                                                (int32_t)(obstacles.size() / 4), 0, inflation, &feasible, &fseg,
+                                                                                &fobs, nullptr, nullptr, nullptr, &lowest);
+  if (rc != MTG_OK) {
+    feasible = 0;
+    fseg = fobs = -1;
+    lowest = std::nan("");
+  }
+  if (first_segment) *first_segment = fseg;
+  if (first_obstacle) *first_obstacle = fobs;
+  if (clearance) *clearance = lowest;
+  return feasible != 0;
+}
 
 }  // namespace mav_trajectory_generation
 #endif

@@ -556,6 +556,58 @@ int mtg_half_planes_from_points_normals(int32_t n, const double* points, const d
  * minimum face (center - size / 2) with normal +e, then the maximum face (center + size / 2) with -e.  Host pointers. */
 int mtg_half_planes_bounding_box(const double* center, const double* size, double* out);
 
+/* ---- next to the half-plane check: batched sphere-obstacle clearance check -----------------------
+ * Replaces, for a batch and a set of spheres, the caller's loop of Trajectory::offsetTrajectory(-centre) followed by
+ * computeMinMaxMagnitude(POSITION, {0, 1, 2}, &min, &max) per obstacle (src/segment.cpp:83-184): which trajectories
+ * stay clear of every sphere, where the others hit first, and by how much each segment misses.
+ * An obstacle is 4 doubles (cx, cy, cz, r).  The clearance of a segment at local time t is
+ *   || p(t) - c || - r - inflation  over dimensions 0-2 (a 4th, yaw, dimension is never read); an obstacle fails a
+ * segment iff !(clearance > 0) at t = 0, t = T or a real root in [0, T] of g = sum_dim (p_dim - c_dim) p_dim'
+ * (Segment::computeMinMaxMagnitudeCandidates of the offset segment), isolated directly as in mtg_minmax_magnitude.
+ * This is a safety check: a NaN clearance FAILS, and a NaN wins every minimum it enters (segment and trajectory).
+ *   n_coeffs                 1 .. 12 (odd counts and counts below 4 run zero-padded in the next even instantiation)
+ *   n_segments               1 .. 2^19 - 1
+ *   dimension                3 or 4
+ *   times                    times[b * times_stride_b + k * times_stride_k]; strides >= 1, [B][K] or [K][B] without
+ *                            overlap; T <= 0: no interior candidates, both ends are still evaluated
+ *   obstacles                trajectory b uses the n_obstacles spheres at obstacles + b * obstacles_stride_b (stride in
+ *                            doubles, >= 0): 0 one shared set, 4 M a set per trajectory
+ *   n_obstacles              1 .. 4096
+ *   inflation                >= 0 and finite: the vehicle's radius, added to every sphere's
+ *   trajectory_feasible      out [batch]; required: 1 / 0
+ *   first_failing_segment    out optional [batch]: first segment in segment order with a failing obstacle, -1 if none
+ *   first_failing_obstacle   out optional [batch]: smallest index among that segment's failing obstacles, -1 if none
+ *   segment_clearance        out optional [batch][K]: minimum over ALL obstacles and candidates (no early exit)
+ *   segment_nearest_obstacle out optional [batch][K]: the obstacle that attains it; a tie goes to the smallest index, a
+ *                            NaN to the smallest index that produced one
+ *   segment_closest_time     out optional [batch][K]: local time of that candidate (of one obstacle's candidates the
+ *                            first in the order 0, T, roots ascending wins a tie).  As for the extremum times of
+ *                            mtg_minmax_magnitude: the VALUE is second order in the root's error, the TIME is not --
+ *                            where the distance is flat (a multiple root of g, a rest-to-rest segment's end) the time is
+ *                            resolved to ~ eps^(1/m) T only
+ *   trajectory_clearance     out optional [batch]: minimum over the segments
+ * The convolution sum_dim p p' is formed once per segment; an obstacle is searched only if a lower bound of its
+ * clearance over the segment's bounding boxes (less a rounding allowance) is not both > 0 and above the running minimum,
+ * nearest bound first: no result depends on the pruning or on the order of the list beyond the index rules above.
+ * Device pointers (radii are not verified); asynchronous on the context's stream, three launches, no workspace,
+ * capturable.  Argument errors: MTG_ERR_INVALID_ARGUMENT, nothing enqueued; batch == 0 returns before anything is.  */
+int mtg_check_obstacle_clearance(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                                 const double* coeffs, const double* times, int64_t times_stride_b,
+                                 int64_t times_stride_k, const double* obstacles, int32_t n_obstacles,
+                                 int64_t obstacles_stride_b, double inflation, int32_t* trajectory_feasible,
+                                 int32_t* first_failing_segment, int32_t* first_failing_obstacle,
+                                 double* segment_clearance, int32_t* segment_nearest_obstacle,
+                                 double* segment_closest_time, double* trajectory_clearance);
+/* The same check with HOST pointers on the library's host build of the same code, synchronous; needs no context and
+ * no device.  Here the obstacles are readable: a radius that is negative or not finite is MTG_ERR_INVALID_ARGUMENT.  */
+int mtg_check_obstacle_clearance_host(int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                                      const double* coeffs, const double* times, int64_t times_stride_b,
+                                      int64_t times_stride_k, const double* obstacles, int32_t n_obstacles,
+                                      int64_t obstacles_stride_b, double inflation, int32_t* trajectory_feasible,
+                                      int32_t* first_failing_segment, int32_t* first_failing_obstacle,
+                                      double* segment_clearance, int32_t* segment_nearest_obstacle,
+                                      double* segment_closest_time, double* trajectory_clearance);
+
 /* ---- the time optimisers' objective with soft constraints ---------------------------------------
  * Replaces, for a batch, the callbacks PolynomialOptimizationNonLinear<N> hands to nlopt
  * (impl/polynomial_optimization_nonlinear_impl.h, NL below): objectiveFunctionTime (NL:556-615) and

@@ -11,6 +11,7 @@ from .core import get_input_feasibility_result_name  # noqa: F401
 from .core import check_input_feasibility_recursive, check_input_feasibility_recursive_host  # noqa: F401
 from .core import half_planes, bounding_box_half_planes, check_half_plane_feasibility, check_half_plane_feasibility_host  # noqa: F401
 from .core import HalfPlaneFeasibilityResult  # noqa: F401
+from .core import sphere_obstacles, check_obstacle_clearance, check_obstacle_clearance_host, ObstacleClearanceResult  # noqa: F401
 from .core import AxisMinMax, minmax_axes, minmax_axes_host, bounding_boxes  # noqa: F401
 from .workload import ends_full_masks, random_waypoint_batch  # noqa: F401
 from .buckets import MergedRequest, MixedBatchSolver  # noqa: F401

@@ -153,6 +153,14 @@ EXPORTS = {
         c_double_p, c_double_p]),
     "mtg_half_planes_from_points_normals": (ctypes.c_int, [ctypes.c_int32, c_double_p, c_double_p, c_double_p]),
     "mtg_half_planes_bounding_box": (ctypes.c_int, [c_double_p, c_double_p, c_double_p]),
+    "mtg_check_obstacle_clearance": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
+        ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p, c_double_p, c_double_p]),
+    "mtg_check_obstacle_clearance_host": (ctypes.c_int, [
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
+        c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        c_double_p, ctypes.c_void_p, c_double_p, c_double_p]),
     "mtg_time_objective_params_init":(None, [ctypes.POINTER(TimeObjectiveParamsC)]),
     "mtg_time_objective": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Layout), c_double_p, c_double_p, c_double_p,
                                           ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p, c_double_p,

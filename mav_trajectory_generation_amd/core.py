@@ -587,6 +587,103 @@ def check_half_plane_feasibility_host(coeffs, times, planes, times_layout: str =
     return HalfPlaneFeasibilityResult(*[a[0] for a in res]) if single else res
 
 
+def sphere_obstacles(centers, radii) -> np.ndarray:
+    """centers [M][3] with radii [M] (or a scalar) -> [M][4] rows (cx, cy, cz, r), the obstacle format of
+    check_obstacle_clearance; centers [B][M][3] with radii [M], [B][M] or a scalar -> [B][M][4], a set per trajectory.
+    A radius that is negative or not finite raises."""
+    centers = np.asarray(centers, dtype=np.float64)
+    if centers.ndim not in (2, 3) or centers.shape[-1] != 3:
+        raise MtgError(-1, "centers must be [M][3] or [B][M][3]")
+    radii = np.broadcast_to(np.asarray(radii, dtype=np.float64), centers.shape[:-1])
+    if not (np.isfinite(radii) & (radii >= 0.0)).all():
+        raise MtgError(-1, "radii must be >= 0 and finite")
+    return np.ascontiguousarray(np.concatenate([centers, radii[..., None]], axis=-1))
+
+
+class ObstacleClearanceResult(NamedTuple):
+    """trajectory_feasible [B] int32 (1 / 0), first_failing_segment [B] int32 (-1: none), first_failing_obstacle [B] int32
+    (-1: none), segment_clearance [B][K], segment_nearest_obstacle [B][K] int32, segment_closest_time [B][K],
+    trajectory_clearance [B] (minimum of ||p(t) - c|| - r - inflation; a NaN wins); the last four None if not asked for."""
+    trajectory_feasible: object
+    first_failing_segment: object
+    first_failing_obstacle: object
+    segment_clearance: object
+    segment_nearest_obstacle: object
+    segment_closest_time: object
+    trajectory_clearance: object
+
+
+def _obstacle_stride(shape, bsz: int):
+    """[M][4]: one set for every trajectory; [B][M][4]: a set per trajectory."""
+    if len(shape) not in (2, 3) or shape[-1] != 4:
+        raise MtgError(-1, "obstacles must be [M][4] or [B][M][4]")
+    m = int(shape[-2])
+    if len(shape) == 3 and shape[0] != bsz:
+        raise MtgError(-1, "obstacles: the batch axis must match coeffs")
+    return m, (4 * m if len(shape) == 3 else 0)
+
+
+def check_obstacle_clearance(ctx: "Context", coeffs, times, obstacles, inflation: float = 0.0, times_layout: str = "aos",
+                             want_clearance: bool = True) -> ObstacleClearanceResult:
+    """Batched clearance of solved trajectories from a set of spheres: coeffs [B][K][D][N] (D = 3 or 4), times ([B][K] 'aos' /
+    [K][B] 'soa') and obstacles ([M][4] or [B][M][4] rows of (cx, cy, cz, r), see sphere_obstacles) as CUDA float64 tensors.
+    An obstacle fails a segment iff not ||p(t) - c|| - r - inflation > 0 at t = 0, T or a critical point of the distance."""
+    import torch
+    bsz, k, dim, n = coeffs.shape
+    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
+    assert obstacles.is_cuda and obstacles.dtype == torch.float64 and obstacles.is_contiguous()
+    m, osb = _obstacle_stride(tuple(obstacles.shape), bsz)
+    dev = coeffs.device
+    feas = torch.empty((bsz,), dtype=torch.int32, device=dev)
+    fseg = torch.empty((bsz,), dtype=torch.int32, device=dev)
+    fobs = torch.empty((bsz,), dtype=torch.int32, device=dev)
+    seg_c = torch.empty((bsz, k), dtype=torch.float64, device=dev) if want_clearance else None
+    seg_o = torch.empty((bsz, k), dtype=torch.int32, device=dev) if want_clearance else None
+    seg_t = torch.empty((bsz, k), dtype=torch.float64, device=dev) if want_clearance else None
+    traj_c = torch.empty((bsz,), dtype=torch.float64, device=dev) if want_clearance else None
+    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    cur = ctx._enter()
+    rc = ctx.lib.mtg_check_obstacle_clearance(ctx.handle, n, k, dim, bsz, ptr(coeffs), ptr(times), sb, sk, ptr(obstacles), m, osb,
+                                              float(inflation), ptr(feas), ptr(fseg), ptr(fobs), ptr(seg_c), ptr(seg_o), ptr(seg_t),
+                                              ptr(traj_c))
+    ctx._leave(cur)
+    _check(ctx.lib, rc, ctx.handle)
+    return ObstacleClearanceResult(feas, fseg, fobs, seg_c, seg_o, seg_t, traj_c)
+
+
+def check_obstacle_clearance_host(coeffs, times, obstacles, inflation: float = 0.0,
+                                  times_layout: str = "aos") -> ObstacleClearanceResult:
+    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
+    [B][K][D][N] or one trajectory [K][D][N] (then obstacles [M][4], results without the batch axis).  A radius that is
+    negative or not finite raises."""
+    lib = L.load()
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    obstacles = np.ascontiguousarray(obstacles, dtype=np.float64)
+    single = coeffs.ndim == 3
+    if single:
+        coeffs, times = coeffs[None], times[None]
+    bsz, k, dim, n = coeffs.shape
+    if times.size != bsz * k:
+        raise MtgError(-1, "times must hold one value per segment")
+    m, osb = _obstacle_stride(obstacles.shape, bsz)
+    feas = np.empty((bsz,), dtype=np.int32)
+    fseg = np.empty((bsz,), dtype=np.int32)
+    fobs = np.empty((bsz,), dtype=np.int32)
+    seg_c = np.empty((bsz, k), dtype=np.float64)
+    seg_o = np.empty((bsz, k), dtype=np.int32)
+    seg_t = np.empty((bsz, k), dtype=np.float64)
+    traj_c = np.empty((bsz,), dtype=np.float64)
+    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
+    rc = lib.mtg_check_obstacle_clearance_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk, obstacles.ctypes.data,
+                                               m, osb, float(inflation), feas.ctypes.data, fseg.ctypes.data, fobs.ctypes.data,
+                                               seg_c.ctypes.data, seg_o.ctypes.data, seg_t.ctypes.data, traj_c.ctypes.data)
+    _check(lib, rc)
+    res = ObstacleClearanceResult(feas, fseg, fobs, seg_c, seg_o, seg_t, traj_c)
+    return ObstacleClearanceResult(*[a[0] for a in res]) if single else res
+
+
 class Plan:
     def __init__(self, ctx: Context, n_coeffs: int, dimension: int, n_segments: int,
                  derivative_to_optimize: Optional[int], fixed_mask: Sequence[int]):
