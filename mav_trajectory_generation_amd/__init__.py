@@ -4,15 +4,16 @@ Host-side plumbing only: the compute path is the hand-written HIP library
 csrc/libmtg_hip.so (C ABI in include/mtg_hip.h).  There is NO CPU fallback: importing the
 solver entry points without the built library, or calling them without a GPU, raises.
 """
-from .core import Context, Plan, MtgError, MultiSolve, solve_linear_batch, library_path, sample_range  # noqa: F401
-from .core import minmax_magnitude, scale_segment_times_to_meet_constraints, pack_multi_items, PackedMultiSolve  # noqa: F401
-from .core import InputConstraints, InputFeasibilityResult, check_input_feasibility, check_input_feasibility_host  # noqa: F401
-from .core import get_input_feasibility_result_name  # noqa: F401
-from .core import check_input_feasibility_recursive, check_input_feasibility_recursive_host  # noqa: F401
-from .core import half_planes, bounding_box_half_planes, check_half_plane_feasibility, check_half_plane_feasibility_host  # noqa: F401
-from .core import HalfPlaneFeasibilityResult  # noqa: F401
-from .core import sphere_obstacles, check_obstacle_clearance, check_obstacle_clearance_host, ObstacleClearanceResult  # noqa: F401
-from .core import AxisMinMax, minmax_axes, minmax_axes_host, bounding_boxes  # noqa: F401
+from .core import Context, Plan, MtgError, MultiSolve, solve_linear_batch, library_path  # noqa: F401
+from .core import pack_multi_items, PackedMultiSolve  # noqa: F401
+from .segment_checks import sample_range, minmax_magnitude, scale_segment_times_to_meet_constraints  # noqa: F401
+from .segment_checks import InputConstraints, InputFeasibilityResult, check_input_feasibility, check_input_feasibility_host  # noqa: F401
+from .segment_checks import get_input_feasibility_result_name  # noqa: F401
+from .segment_checks import check_input_feasibility_recursive, check_input_feasibility_recursive_host  # noqa: F401
+from .segment_checks import half_planes, bounding_box_half_planes, check_half_plane_feasibility  # noqa: F401
+from .segment_checks import check_half_plane_feasibility_host, HalfPlaneFeasibilityResult  # noqa: F401
+from .segment_checks import sphere_obstacles, check_obstacle_clearance, check_obstacle_clearance_host, ObstacleClearanceResult  # noqa: F401
+from .segment_checks import AxisMinMax, minmax_axes, minmax_axes_host, bounding_boxes  # noqa: F401
 from .workload import ends_full_masks, random_waypoint_batch  # noqa: F401
 from .buckets import MergedRequest, MixedBatchSolver  # noqa: F401
 from .time_gradient import mellinger_cost_and_gradient  # noqa: F401

@@ -44,6 +44,19 @@ class TimeObjectiveParamsC(ctypes.Structure):   # mtg_time_objective_params
                 ("derivative", ctypes.c_int32 * 4), ("value", ctypes.c_double * 4)]
 
 
+# what every per-segment entry (segment_checks.py) starts with: N, K, D, B, coeffs, times, times_stride_b, times_stride_k
+_SEGMENT = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64]
+
+
+def _segment_entry(name, tail, host=True):
+    """The prototypes of a per-segment entry: `name` takes the context, the shared arguments and its own `tail`; its host twin
+    `name`_host (for the entries that have one) the same without the context."""
+    entry = {name: (ctypes.c_int, [ctypes.c_void_p] + _SEGMENT + tail)}
+    if host:
+        entry[name + "_host"] = (ctypes.c_int, _SEGMENT + tail)
+    return entry
+
+
 EXPORTS = {
     "mtg_context_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "mtg_context_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -111,66 +124,30 @@ EXPORTS = {
     "mtg_device_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mtg_copy_to_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     "mtg_copy_to_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
-    "mtg_sample_range": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                        c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
-                                        ctypes.c_double, ctypes.c_int32, ctypes.c_int32, c_double_p, ctypes.c_void_p]),
-    "mtg_minmax_magnitude": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                            c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                            ctypes.c_uint32, c_double_p, c_double_p, ctypes.c_void_p]),
-    "mtg_minmax_axes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                       c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                       c_double_p, c_double_p, ctypes.c_void_p]),
-    "mtg_minmax_axes_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p,
-                                            c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                            c_double_p, c_double_p, ctypes.c_void_p]),
-    "mtg_scale_segment_times_to_meet_constraints": (ctypes.c_int, [
-        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, c_double_p, c_double_p,
-        ctypes.c_void_p]),
+    **_segment_entry("mtg_sample_range", [ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, c_double_p,
+                                          ctypes.c_void_p], host=False),
+    **_segment_entry("mtg_minmax_magnitude", [ctypes.c_int32, ctypes.c_uint32, c_double_p, c_double_p, ctypes.c_void_p], host=False),
+    **_segment_entry("mtg_minmax_axes", [ctypes.c_int32, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_void_p]),
+    **_segment_entry("mtg_scale_segment_times_to_meet_constraints", [ctypes.c_double, ctypes.c_double, ctypes.c_int32, c_double_p,
+                                                                     c_double_p, ctypes.c_void_p], host=False),
     "mtg_input_constraints_init": (None, [ctypes.POINTER(InputConstraintsC)]),
     "mtg_input_constraints_set_defaults": (None, [ctypes.POINTER(InputConstraintsC)]),
-    "mtg_check_input_feasibility": (ctypes.c_int, [
-        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
-        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        c_double_p]),
-    "mtg_check_input_feasibility_host": (ctypes.c_int, [
-        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
-        ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p]),
-    "mtg_check_input_feasibility_recursive": (ctypes.c_int, [
-        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
-        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        c_double_p, ctypes.c_void_p]),
-    "mtg_check_input_feasibility_recursive_host": (ctypes.c_int, [
-        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
-        ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p]),
-    "mtg_check_half_plane_feasibility": (ctypes.c_int, [
-        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
-        ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, c_double_p, c_double_p]),
-    "mtg_check_half_plane_feasibility_host": (ctypes.c_int, [
-        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
-        c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        c_double_p, c_double_p]),
+    **_segment_entry("mtg_check_input_feasibility", [ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, c_double_p]),
+    **_segment_entry("mtg_check_input_feasibility_recursive", [ctypes.POINTER(InputConstraintsC), ctypes.c_void_p, ctypes.c_void_p,
+                                                               ctypes.c_void_p, c_double_p, ctypes.c_void_p]),
+    **_segment_entry("mtg_check_half_plane_feasibility", [c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_void_p, c_double_p, c_double_p]),
     "mtg_half_planes_from_points_normals": (ctypes.c_int, [ctypes.c_int32, c_double_p, c_double_p, c_double_p]),
     "mtg_half_planes_bounding_box": (ctypes.c_int, [c_double_p, c_double_p, c_double_p]),
-    "mtg_check_obstacle_clearance": (ctypes.c_int, [
-        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p,
-        ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p, c_double_p, c_double_p]),
-    "mtg_check_obstacle_clearance_host": (ctypes.c_int, [
-        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
-        c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        c_double_p, ctypes.c_void_p, c_double_p, c_double_p]),
+    **_segment_entry("mtg_check_obstacle_clearance", [c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p, c_double_p,
+                                                      c_double_p]),
     "mtg_time_objective_params_init":(None, [ctypes.POINTER(TimeObjectiveParamsC)]),
     "mtg_time_objective": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Layout), c_double_p, c_double_p, c_double_p,
                                           ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p, c_double_p,
                                           c_double_p]),
-    "mtg_magnitude_soft_cost": (ctypes.c_int, [
-        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64,
-        ctypes.c_int64, ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p]),
-    "mtg_magnitude_soft_cost_host": (ctypes.c_int, [
-        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64,
-        ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p]),
+    **_segment_entry("mtg_magnitude_soft_cost", [ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p]),
     "mtg_time_cost_host": (ctypes.c_int, [ctypes.POINTER(TimeObjectiveParamsC), ctypes.c_int32, ctypes.c_int64, c_double_p,
                                           ctypes.c_int64, ctypes.c_int64, c_double_p]),
     "mtg_multi_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(MultiItem), ctypes.c_uint32,

@@ -3,14 +3,14 @@
 Mirrors the reference call sequence (polynomial_optimization_linear.h:57-108):
     PolynomialOptimization<N> opt(D); opt.setupFromVertices(vertices, times, d); opt.solveLinear();
 as  plan = Plan(ctx, N, D, K, d, fixed_mask); plan.solve(times, d_fixed) -> coeffs [B][K][D][N]
-for a whole batch of trajectories sharing the constraint structure.
+for a whole batch of trajectories sharing the constraint structure.  What is then done with the solved batch -- sampling,
+extrema, the feasibility checks -- is in segment_checks.py.
 torch is used only to own device memory and streams.
 """
 from __future__ import annotations
 
 import ctypes
-import enum
-from typing import NamedTuple, Optional, Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -134,554 +134,6 @@ class Context:
             self.close()
         except Exception:
             pass
-
-
-def sample_range(ctx: "Context", coeffs, times, t_start: float, dt: float, n_samples: int, n_derivatives: int = 5,
-                 times_layout: str = "aos", want_valid: bool = False, out=None, valid=None):
-    """Batched Trajectory::evaluateRange / sampleTrajectoryInRange: coeffs [B][K][D][N] and times ([B][K] 'aos' or
-    [K][B] 'soa') CUDA tensors -> out [B][n_samples][n_derivatives][D] (and n_valid [B] int32).
-    `out` / `valid`: caller-owned result buffers (float64 / int32 CUDA tensors of exactly that many elements on the device of
-    `coeffs`, contiguous, `out` 16-byte aligned) instead of fresh allocations; `valid` implies want_valid.  The results are
-    views of them in the shapes above."""
-    import torch
-    bsz, k, dim, n = coeffs.shape
-    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
-    shape = (bsz, n_samples, n_derivatives, dim)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float64, device=coeffs.device)
-    else:
-        if not (out.is_cuda and out.device == coeffs.device and out.dtype == torch.float64):
-            raise ValueError("sample_range: `out` must be a float64 tensor on the device of `coeffs`")
-        if out.numel() != bsz * n_samples * n_derivatives * dim or not out.is_contiguous():
-            raise ValueError("sample_range: `out` must be contiguous with %d x %d x %d x %d elements" % shape)
-        if out.data_ptr() % 16:
-            raise ValueError("sample_range: `out` must be 16-byte aligned")
-        out = out.view(shape)
-    if valid is None:
-        valid = torch.empty((bsz,), dtype=torch.int32, device=coeffs.device) if want_valid else None
-    else:
-        if not (valid.is_cuda and valid.device == coeffs.device and valid.dtype == torch.int32):
-            raise ValueError("sample_range: `valid` must be an int32 tensor on the device of `coeffs`")
-        if valid.numel() != bsz or not valid.is_contiguous():
-            raise ValueError("sample_range: `valid` must be contiguous with %d elements" % bsz)
-        valid = valid.view((bsz,))
-        want_valid = True
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    cur = ctx._enter()
-    rc = ctx.lib.mtg_sample_range(ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()),
-                                  ctypes.c_void_p(times.data_ptr()), sb, sk, float(t_start), float(dt), n_samples,
-                                  n_derivatives, ctypes.c_void_p(out.data_ptr()),
-                                  ctypes.c_void_p(valid.data_ptr()) if valid is not None else None)
-    ctx._leave(cur)
-    _check(ctx.lib, rc, ctx.handle)
-    return (out, valid) if want_valid else out
-
-
-def minmax_magnitude(ctx: "Context", coeffs, times, derivative: int, dimensions: Optional[Sequence[int]] = None,
-                     times_layout: str = "aos"):
-    """Batched Trajectory::computeMinMaxMagnitude: coeffs [B][K][D][N], times ([B][K] 'aos' / [K][B] 'soa') CUDA
-    tensors -> (segment_minmax [B][K][4], trajectory_minmax [B][4], trajectory_segment_idx [B][2] int32); the four
-    columns are (t_min, v_min, t_max, v_max) with segment-local times."""
-    import torch
-    bsz, k, dim, n = coeffs.shape
-    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
-    mask = 0
-    for d in (dimensions if dimensions is not None else range(dim)):
-        if d < 0 or d >= dim:
-            raise MtgError(-1, "dimension %d out of bounds [0..%d]" % (d, dim - 1))
-        mask |= 1 << d
-    seg = torch.empty((bsz, k, 4), dtype=torch.float64, device=coeffs.device)
-    traj = torch.empty((bsz, 4), dtype=torch.float64, device=coeffs.device)
-    idx = torch.empty((bsz, 2), dtype=torch.int32, device=coeffs.device)
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    cur = ctx._enter()
-    rc = ctx.lib.mtg_minmax_magnitude(ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()),
-                                      ctypes.c_void_p(times.data_ptr()), sb, sk, int(derivative), mask,
-                                      ctypes.c_void_p(seg.data_ptr()), ctypes.c_void_p(traj.data_ptr()),
-                                      ctypes.c_void_p(idx.data_ptr()))
-    ctx._leave(cur)
-    _check(ctx.lib, rc, ctx.handle)
-    return seg, traj, idx
-
-
-class AxisMinMax(NamedTuple):
-    """segment [B][K][D][n][4], trajectory [B][D][n][4] or None, trajectory_segment_idx [B][D][n][2] int32 or None; the four
-    columns are (t_min, v_min, t_max, v_max) with segment-local times, n the orders asked for."""
-    segment: object
-    trajectory: object
-    trajectory_segment_idx: object
-
-
-def minmax_axes(ctx: "Context", coeffs, times, derivative_first: int = 0, n_derivatives: int = 1, times_layout: str = "aos",
-                want_trajectory: bool = True) -> AxisMinMax:
-    """Batched Polynomial::computeMinMax: the signed minimum and maximum of every axis over every segment, for the orders
-    derivative_first .. derivative_first + n_derivatives - 1 (0 = position .. 4 = snap) from one root search per axis.  coeffs
-    [B][K][D][N], times ([B][K] 'aos' / [K][B] 'soa') CUDA float64 tensors.  A row with a NaN candidate is (0, NaN, 0, NaN)."""
-    import torch
-    bsz, k, dim, n = coeffs.shape
-    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
-    nd = int(n_derivatives)
-    if nd < 1 or nd > 5:
-        raise MtgError(-1, "n_derivatives must be in [1, 5]")
-    dev = coeffs.device
-    seg = torch.empty((bsz, k, dim, nd, 4), dtype=torch.float64, device=dev)
-    traj = torch.empty((bsz, dim, nd, 4), dtype=torch.float64, device=dev) if want_trajectory else None
-    idx = torch.empty((bsz, dim, nd, 2), dtype=torch.int32, device=dev) if want_trajectory else None
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    cur = ctx._enter()
-    rc = ctx.lib.mtg_minmax_axes(ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()), ctypes.c_void_p(times.data_ptr()),
-                                 sb, sk, int(derivative_first), nd, ctypes.c_void_p(seg.data_ptr()),
-                                 ctypes.c_void_p(traj.data_ptr()) if traj is not None else None,
-                                 ctypes.c_void_p(idx.data_ptr()) if idx is not None else None)
-    ctx._leave(cur)
-    _check(ctx.lib, rc, ctx.handle)
-    return AxisMinMax(seg, traj, idx)
-
-
-def minmax_axes_host(coeffs, times, derivative_first: int = 0, n_derivatives: int = 1, times_layout: str = "aos",
-                     want_trajectory: bool = True) -> AxisMinMax:
-    """The same on numpy arrays through the library's host build of the same code (no context, no device): coeffs
-    [B][K][D][N] or one trajectory [K][D][N] (then the results come without the batch axis)."""
-    lib = L.load()
-    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
-    times = np.ascontiguousarray(times, dtype=np.float64)
-    single = coeffs.ndim == 3
-    if single:
-        coeffs, times = coeffs[None], times[None]
-    bsz, k, dim, n = coeffs.shape
-    if times.size != bsz * k:
-        raise MtgError(-1, "times must hold one value per segment")
-    nd = int(n_derivatives)
-    if nd < 1 or nd > 5:
-        raise MtgError(-1, "n_derivatives must be in [1, 5]")
-    seg = np.empty((bsz, k, dim, nd, 4), dtype=np.float64)
-    traj = np.empty((bsz, dim, nd, 4), dtype=np.float64) if want_trajectory else None
-    idx = np.empty((bsz, dim, nd, 2), dtype=np.int32) if want_trajectory else None
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    rc = lib.mtg_minmax_axes_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk, int(derivative_first), nd,
-                                  seg.ctypes.data, traj.ctypes.data if traj is not None else None,
-                                  idx.ctypes.data if idx is not None else None)
-    _check(lib, rc)
-    res = AxisMinMax(seg, traj, idx)
-    return AxisMinMax(*[a if a is None else a[0] for a in res]) if single else res
-
-
-def bounding_boxes(ctx: "Context", coeffs, times, times_layout: str = "aos", margin: float = 0.0):
-    """Axis-aligned bounding boxes of position from one minmax_axes call of order 0: (segment_lo_hi [B][K][2][D],
-    trajectory_lo_hi [B][2][D]), lo - margin / hi + margin."""
-    import torch
-    r = minmax_axes(ctx, coeffs, times, 0, 1, times_layout, True)
-    seg = torch.stack([r.segment[:, :, :, 0, 1] - margin, r.segment[:, :, :, 0, 3] + margin], dim=2)
-    traj = torch.stack([r.trajectory[:, :, 0, 1] - margin, r.trajectory[:, :, 0, 3] + margin], dim=1)
-    return seg, traj
-
-
-def scale_segment_times_to_meet_constraints(ctx: "Context", coeffs, times, v_max: float, a_max: float,
-                                            max_iterations: int = 2, times_layout: str = "aos", workspace=None):
-    """Batched Trajectory::scaleSegmentTimesToMeetConstraints, IN PLACE on coeffs [B][K][D][N] and times.
-    Returns (scaling [B], within_range [B] int32, workspace); workspace[2*B*K*4:].view(2, B, 4)[:, :, 3] are the
-    maximum |velocity| / |acceleration| seen by the last round's check."""
-    import torch
-    bsz, k, dim, n = coeffs.shape
-    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
-    need = 8 * bsz * (k + 1)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.float64, device=coeffs.device)
-    assert workspace.numel() >= need and workspace.dtype == torch.float64
-    scaling = torch.empty((bsz,), dtype=torch.float64, device=coeffs.device)
-    within = torch.empty((bsz,), dtype=torch.int32, device=coeffs.device)
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    cur = ctx._enter()
-    rc = ctx.lib.mtg_scale_segment_times_to_meet_constraints(
-        ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()), ctypes.c_void_p(times.data_ptr()), sb, sk,
-        float(v_max), float(a_max), int(max_iterations), ctypes.c_void_p(workspace.data_ptr()),
-        ctypes.c_void_p(scaling.data_ptr()), ctypes.c_void_p(within.data_ptr()))
-    ctx._leave(cur)
-    _check(ctx.lib, rc, ctx.handle)
-    return scaling, within, workspace
-
-
-class InputFeasibilityResult(enum.IntEnum):
-    """The reference's enum InputFeasibilityResult (mav_trajectory_generation_ros feasibility_base.h:34-50)."""
-    kInputFeasible = 0
-    kInputIndeterminable = 1
-    kInputInfeasibleThrustHigh = 2
-    kInputInfeasibleThrustLow = 3
-    kInputInfeasibleVelocity = 4
-    kInputInfeasibleRollPitchRates = 5
-    kInputInfeasibleYawRates = 6
-    kInputInfeasibleYawAcc = 7
-
-
-_RESULT_NAMES = ("Feasible", "Indeterminable", "InfeasibleThrustHigh", "InfeasibleThrustLow", "InfeasibleVelocity",
-                 "InfeasibleRollPitchRates", "InfeasibleYawRates", "InfeasibleYawAcc")
-
-
-def get_input_feasibility_result_name(result: int) -> str:
-    """getInputFeasibilityResultName: the enumerator without its kInput prefix."""
-    result = int(result)
-    return _RESULT_NAMES[result] if 0 <= result < len(_RESULT_NAMES) else "Unknown!"
-
-
-class InputConstraints:
-    """The reference's InputConstraints (input_constraints.h): up to six optional limits, stored by magnitude.  Adding f_min
-    while f_max exists raises f_max to at least it, and the mirror case.  gravity enters the thrust ||a + (0, 0, gravity)||
-    and the default thrust limits; min_section_time_s is FeasibilityAnalytic::Settings' (stored by magnitude too)."""
-    NAMES = ("f_min", "f_max", "v_max", "omega_xy_max", "omega_z_max", "omega_z_dot_max")
-    GRAVITY = 9.81   # mav_msgs::kGravity upstream
-
-    def __init__(self, min_section_time_s: float = 0.05, gravity: float = GRAVITY, **limits):
-        self.constraints = {}
-        self.min_section_time_s = abs(float(min_section_time_s))
-        self.gravity = float(gravity)
-        for name, value in limits.items():
-            self.add_constraint(name, value)
-
-    @classmethod
-    def defaults(cls, **kw) -> "InputConstraints":
-        c = cls(**kw)
-        c.set_default_values()
-        return c
-
-    def add_constraint(self, name: str, value: float):
-        if name not in self.NAMES:
-            raise KeyError(name)
-        value = abs(float(value))
-        if name == "f_min" and "f_max" in self.constraints:
-            self.constraints["f_max"] = max(value, self.constraints["f_max"])
-        elif name == "f_max" and "f_min" in self.constraints:
-            self.constraints["f_min"] = min(value, self.constraints["f_min"])
-        self.constraints[name] = value
-
-    def set_default_values(self):
-        import math
-        self.constraints.update(f_min=0.5 * self.gravity, f_max=1.5 * self.gravity, v_max=3.0, omega_xy_max=math.pi / 2.0,
-                                omega_z_max=math.pi / 2.0, omega_z_dot_max=2.0 * math.pi)
-
-    def has_constraint(self, name: str) -> bool:
-        return name in self.constraints
-
-    def get_constraint(self, name: str) -> Optional[float]:
-        return self.constraints.get(name)
-
-    def remove_constraint(self, name: str) -> bool:
-        return self.constraints.pop(name, None) is not None
-
-    def to_c(self) -> L.InputConstraintsC:
-        c = L.InputConstraintsC(*[self.constraints.get(n, float("nan")) for n in self.NAMES], self.min_section_time_s, self.gravity)
-        return c
-
-
-def check_input_feasibility(ctx: "Context", coeffs, times, constraints: InputConstraints, times_layout: str = "aos",
-                            want_segments: bool = True, want_bounds: bool = True):
-    """Batched FeasibilityAnalytic::checkInputFeasibilityTrajectory: coeffs [B][K][D][N], times ([B][K] 'aos' / [K][B] 'soa')
-    CUDA tensors -> (trajectory_result [B] int32, first_failing_segment [B] int32 (-1: none), segment_result [B][K] int32 or
-    None, segment_bounds [B][K][6] or None: thrust min, thrust max, velocity max, whole-segment roll/pitch bound, |yaw rate|
-    max, |yaw acceleration| max; NaN where not computed).  Result codes: InputFeasibilityResult."""
-    import torch
-    bsz, k, dim, n = coeffs.shape
-    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
-    dev = coeffs.device
-    traj = torch.empty((bsz,), dtype=torch.int32, device=dev)
-    first = torch.empty((bsz,), dtype=torch.int32, device=dev)
-    seg = torch.empty((bsz, k), dtype=torch.int32, device=dev) if want_segments else None
-    bounds = torch.empty((bsz, k, 6), dtype=torch.float64, device=dev) if want_bounds else None
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    c = constraints.to_c()
-    cur = ctx._enter()
-    rc = ctx.lib.mtg_check_input_feasibility(ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()),
-                                             ctypes.c_void_p(times.data_ptr()), sb, sk, ctypes.byref(c),
-                                             ctypes.c_void_p(traj.data_ptr()), ctypes.c_void_p(first.data_ptr()),
-                                             ctypes.c_void_p(seg.data_ptr()) if seg is not None else None,
-                                             ctypes.c_void_p(bounds.data_ptr()) if bounds is not None else None)
-    ctx._leave(cur)
-    _check(ctx.lib, rc, ctx.handle)
-    return traj, first, seg, bounds
-
-
-def check_input_feasibility_host(coeffs, times, constraints: InputConstraints, times_layout: str = "aos"):
-    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
-    [B][K][D][N] or one trajectory [K][D][N]; returns numpy (trajectory_result, first_failing_segment, segment_result,
-    segment_bounds), shaped as the device form's (without the batch axis for one trajectory)."""
-    lib = L.load()
-    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
-    times = np.ascontiguousarray(times, dtype=np.float64)
-    single = coeffs.ndim == 3
-    if single:
-        coeffs, times = coeffs[None], times[None]
-    bsz, k, dim, n = coeffs.shape
-    if times.size != bsz * k:
-        raise MtgError(-1, "times must hold one value per segment")
-    traj = np.empty((bsz,), dtype=np.int32)
-    first = np.empty((bsz,), dtype=np.int32)
-    seg = np.empty((bsz, k), dtype=np.int32)
-    bounds = np.empty((bsz, k, 6), dtype=np.float64)
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    c = constraints.to_c()
-    rc = lib.mtg_check_input_feasibility_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk, ctypes.byref(c),
-                                              traj.ctypes.data, first.ctypes.data, seg.ctypes.data, bounds.ctypes.data)
-    _check(lib, rc)
-    if single:
-        return traj[0], first[0], seg[0], bounds[0]
-    return traj, first, seg, bounds
-
-
-def check_input_feasibility_recursive(ctx: "Context", coeffs, times, constraints: InputConstraints, times_layout: str = "aos",
-                                      want_segments: bool = True, want_bounds: bool = True, want_sections: bool = False):
-    """Batched FeasibilityRecursive::checkInputFeasibilityTrajectory (Mueller's recursive test on single-axis extrema, the cheap
-    and conservative checker): the arguments of check_input_feasibility -> (trajectory_result [B] int32, first_failing_segment
-    [B] int32 (-1: none), segment_result [B][K] int32 or None, segment_bounds [B][K][6] or None: f_lower_bound, f_upper_bound,
-    v_upper_bound and roll/pitch bound of the whole-segment section [0, T], |yaw rate| max, |yaw acceleration| max; NaN where
-    not computed, segment_sections [B][K] int32 or None: the sections the walk examined).  constraints.min_section_time_s is
-    FeasibilityRecursive::Settings' value.  Result codes: InputFeasibilityResult."""
-    import torch
-    bsz, k, dim, n = coeffs.shape
-    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
-    dev = coeffs.device
-    traj = torch.empty((bsz,), dtype=torch.int32, device=dev)
-    first = torch.empty((bsz,), dtype=torch.int32, device=dev)
-    seg = torch.empty((bsz, k), dtype=torch.int32, device=dev) if want_segments else None
-    bounds = torch.empty((bsz, k, 6), dtype=torch.float64, device=dev) if want_bounds else None
-    sections = torch.empty((bsz, k), dtype=torch.int32, device=dev) if want_sections else None
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    c = constraints.to_c()
-    cur = ctx._enter()
-    rc = ctx.lib.mtg_check_input_feasibility_recursive(
-        ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()), ctypes.c_void_p(times.data_ptr()), sb, sk, ctypes.byref(c),
-        ctypes.c_void_p(traj.data_ptr()), ctypes.c_void_p(first.data_ptr()),
-        ctypes.c_void_p(seg.data_ptr()) if seg is not None else None,
-        ctypes.c_void_p(bounds.data_ptr()) if bounds is not None else None,
-        ctypes.c_void_p(sections.data_ptr()) if sections is not None else None)
-    ctx._leave(cur)
-    _check(ctx.lib, rc, ctx.handle)
-    return traj, first, seg, bounds, sections
-
-
-def check_input_feasibility_recursive_host(coeffs, times, constraints: InputConstraints, times_layout: str = "aos"):
-    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
-    [B][K][D][N] or one trajectory [K][D][N]; returns numpy (trajectory_result, first_failing_segment, segment_result,
-    segment_bounds, segment_sections), shaped as the device form's (without the batch axis for one trajectory)."""
-    lib = L.load()
-    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
-    times = np.ascontiguousarray(times, dtype=np.float64)
-    single = coeffs.ndim == 3
-    if single:
-        coeffs, times = coeffs[None], times[None]
-    bsz, k, dim, n = coeffs.shape
-    if times.size != bsz * k:
-        raise MtgError(-1, "times must hold one value per segment")
-    traj = np.empty((bsz,), dtype=np.int32)
-    first = np.empty((bsz,), dtype=np.int32)
-    seg = np.empty((bsz, k), dtype=np.int32)
-    bounds = np.empty((bsz, k, 6), dtype=np.float64)
-    sections = np.empty((bsz, k), dtype=np.int32)
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    c = constraints.to_c()
-    rc = lib.mtg_check_input_feasibility_recursive_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk,
-                                                        ctypes.byref(c), traj.ctypes.data, first.ctypes.data, seg.ctypes.data,
-                                                        bounds.ctypes.data, sections.ctypes.data)
-    _check(lib, rc)
-    if single:
-        return traj[0], first[0], seg[0], bounds[0], sections[0]
-    return traj, first, seg, bounds, sections
-
-
-def half_planes(points, normals) -> np.ndarray:
-    """HalfPlane(point, normal) for n planes: points [n][3], normals [n][3] (any length > 0) -> [n][4] rows (unit normal,
-    offset = point . normal), the plane format of check_half_plane_feasibility.  A zero normal raises."""
-    lib = L.load()
-    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    normals = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
-    if points.shape != normals.shape:
-        raise MtgError(-1, "one point per normal")
-    out = np.empty((points.shape[0], 4), dtype=np.float64)
-    _check(lib, lib.mtg_half_planes_from_points_normals(points.shape[0], points.ctypes.data, normals.ctypes.data, out.ctypes.data))
-    return out
-
-
-def bounding_box_half_planes(center, size) -> np.ndarray:
-    """HalfPlane::createBoundingBox(center, size) -> [6][4]: per axis the minimum face with +e, then the maximum face with -e."""
-    lib = L.load()
-    center = np.ascontiguousarray(center, dtype=np.float64).reshape(3)
-    size = np.ascontiguousarray(size, dtype=np.float64).reshape(3)
-    out = np.empty((6, 4), dtype=np.float64)
-    _check(lib, lib.mtg_half_planes_bounding_box(center.ctypes.data, size.ctypes.data, out.ctypes.data))
-    return out
-
-
-class HalfPlaneFeasibilityResult(NamedTuple):
-    """trajectory_feasible [B] int32 (1 / 0), first_failing_segment [B] int32 (-1: none), first_failing_plane [B] int32
-    (-1: none), segment_clearance [B][K] or None, trajectory_clearance [B] or None (minimum signed distance to the planes)."""
-    trajectory_feasible: object
-    first_failing_segment: object
-    first_failing_plane: object
-    segment_clearance: object
-    trajectory_clearance: object
-
-
-def _plane_strides(shape, bsz: int, k: int):
-    """[P][4]: one set for everything; [K][P][4]: one cell per segment; [B][K][P][4]: a corridor per trajectory."""
-    if len(shape) not in (2, 3, 4) or shape[-1] != 4:
-        raise MtgError(-1, "planes must be [P][4], [K][P][4] or [B][K][P][4]")
-    p = int(shape[-2])
-    if len(shape) >= 3 and shape[-3] != k or len(shape) == 4 and shape[0] != bsz:
-        raise MtgError(-1, "planes: the segment / batch axes must match coeffs")
-    return p, (4 * p * k if len(shape) == 4 else 0), (4 * p if len(shape) >= 3 else 0)
-
-
-def check_half_plane_feasibility(ctx: "Context", coeffs, times, planes, times_layout: str = "aos",
-                                 want_clearance: bool = True) -> HalfPlaneFeasibilityResult:
-    """Batched FeasibilityBase::checkHalfPlaneFeasibility(Trajectory): coeffs [B][K][D][N], times ([B][K] 'aos' / [K][B] 'soa')
-    and planes ([P][4], [K][P][4] or [B][K][P][4] rows of (unit normal, offset), see half_planes) as CUDA float64 tensors.
-    A plane fails a segment iff n . p(t) - offset <= 0 at t = 0, T or a critical point of the projection."""
-    import torch
-    bsz, k, dim, n = coeffs.shape
-    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
-    assert planes.is_cuda and planes.dtype == torch.float64 and planes.is_contiguous()
-    p, psb, psk = _plane_strides(tuple(planes.shape), bsz, k)
-    dev = coeffs.device
-    feas = torch.empty((bsz,), dtype=torch.int32, device=dev)
-    fseg = torch.empty((bsz,), dtype=torch.int32, device=dev)
-    fplane = torch.empty((bsz,), dtype=torch.int32, device=dev)
-    seg_c = torch.empty((bsz, k), dtype=torch.float64, device=dev) if want_clearance else None
-    traj_c = torch.empty((bsz,), dtype=torch.float64, device=dev) if want_clearance else None
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    cur = ctx._enter()
-    rc = ctx.lib.mtg_check_half_plane_feasibility(ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()),
-                                                  ctypes.c_void_p(times.data_ptr()), sb, sk, ctypes.c_void_p(planes.data_ptr()),
-                                                  p, psb, psk, ctypes.c_void_p(feas.data_ptr()), ctypes.c_void_p(fseg.data_ptr()),
-                                                  ctypes.c_void_p(fplane.data_ptr()),
-                                                  ctypes.c_void_p(seg_c.data_ptr()) if seg_c is not None else None,
-                                                  ctypes.c_void_p(traj_c.data_ptr()) if traj_c is not None else None)
-    ctx._leave(cur)
-    _check(ctx.lib, rc, ctx.handle)
-    return HalfPlaneFeasibilityResult(feas, fseg, fplane, seg_c, traj_c)
-
-
-def check_half_plane_feasibility_host(coeffs, times, planes, times_layout: str = "aos") -> HalfPlaneFeasibilityResult:
-    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
-    [B][K][D][N] or one trajectory [K][D][N] (then planes [P][4] or [K][P][4], results without the batch axis).  Normals
-    that are not of unit length raise."""
-    lib = L.load()
-    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
-    times = np.ascontiguousarray(times, dtype=np.float64)
-    planes = np.ascontiguousarray(planes, dtype=np.float64)
-    single = coeffs.ndim == 3
-    if single:
-        coeffs, times = coeffs[None], times[None]
-    bsz, k, dim, n = coeffs.shape
-    if times.size != bsz * k:
-        raise MtgError(-1, "times must hold one value per segment")
-    p, psb, psk = _plane_strides(planes.shape, bsz, k)
-    feas = np.empty((bsz,), dtype=np.int32)
-    fseg = np.empty((bsz,), dtype=np.int32)
-    fplane = np.empty((bsz,), dtype=np.int32)
-    seg_c = np.empty((bsz, k), dtype=np.float64)
-    traj_c = np.empty((bsz,), dtype=np.float64)
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    rc = lib.mtg_check_half_plane_feasibility_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk, planes.ctypes.data,
-                                                   p, psb, psk, feas.ctypes.data, fseg.ctypes.data, fplane.ctypes.data,
-                                                   seg_c.ctypes.data, traj_c.ctypes.data)
-    _check(lib, rc)
-    res = HalfPlaneFeasibilityResult(feas, fseg, fplane, seg_c, traj_c)
-    return HalfPlaneFeasibilityResult(*[a[0] for a in res]) if single else res
-
-
-def sphere_obstacles(centers, radii) -> np.ndarray:
-    """centers [M][3] with radii [M] (or a scalar) -> [M][4] rows (cx, cy, cz, r), the obstacle format of
-    check_obstacle_clearance; centers [B][M][3] with radii [M], [B][M] or a scalar -> [B][M][4], a set per trajectory.
-    A radius that is negative or not finite raises."""
-    centers = np.asarray(centers, dtype=np.float64)
-    if centers.ndim not in (2, 3) or centers.shape[-1] != 3:
-        raise MtgError(-1, "centers must be [M][3] or [B][M][3]")
-    radii = np.broadcast_to(np.asarray(radii, dtype=np.float64), centers.shape[:-1])
-    if not (np.isfinite(radii) & (radii >= 0.0)).all():
-        raise MtgError(-1, "radii must be >= 0 and finite")
-    return np.ascontiguousarray(np.concatenate([centers, radii[..., None]], axis=-1))
-
-
-class ObstacleClearanceResult(NamedTuple):
-    """trajectory_feasible [B] int32 (1 / 0), first_failing_segment [B] int32 (-1: none), first_failing_obstacle [B] int32
-    (-1: none), segment_clearance [B][K], segment_nearest_obstacle [B][K] int32, segment_closest_time [B][K],
-    trajectory_clearance [B] (minimum of ||p(t) - c|| - r - inflation; a NaN wins); the last four None if not asked for."""
-    trajectory_feasible: object
-    first_failing_segment: object
-    first_failing_obstacle: object
-    segment_clearance: object
-    segment_nearest_obstacle: object
-    segment_closest_time: object
-    trajectory_clearance: object
-
-
-def _obstacle_stride(shape, bsz: int):
-    """[M][4]: one set for every trajectory; [B][M][4]: a set per trajectory."""
-    if len(shape) not in (2, 3) or shape[-1] != 4:
-        raise MtgError(-1, "obstacles must be [M][4] or [B][M][4]")
-    m = int(shape[-2])
-    if len(shape) == 3 and shape[0] != bsz:
-        raise MtgError(-1, "obstacles: the batch axis must match coeffs")
-    return m, (4 * m if len(shape) == 3 else 0)
-
-
-def check_obstacle_clearance(ctx: "Context", coeffs, times, obstacles, inflation: float = 0.0, times_layout: str = "aos",
-                             want_clearance: bool = True) -> ObstacleClearanceResult:
-    """Batched clearance of solved trajectories from a set of spheres: coeffs [B][K][D][N] (D = 3 or 4), times ([B][K] 'aos' /
-    [K][B] 'soa') and obstacles ([M][4] or [B][M][4] rows of (cx, cy, cz, r), see sphere_obstacles) as CUDA float64 tensors.
-    An obstacle fails a segment iff not ||p(t) - c|| - r - inflation > 0 at t = 0, T or a critical point of the distance."""
-    import torch
-    bsz, k, dim, n = coeffs.shape
-    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
-    assert obstacles.is_cuda and obstacles.dtype == torch.float64 and obstacles.is_contiguous()
-    m, osb = _obstacle_stride(tuple(obstacles.shape), bsz)
-    dev = coeffs.device
-    feas = torch.empty((bsz,), dtype=torch.int32, device=dev)
-    fseg = torch.empty((bsz,), dtype=torch.int32, device=dev)
-    fobs = torch.empty((bsz,), dtype=torch.int32, device=dev)
-    seg_c = torch.empty((bsz, k), dtype=torch.float64, device=dev) if want_clearance else None
-    seg_o = torch.empty((bsz, k), dtype=torch.int32, device=dev) if want_clearance else None
-    seg_t = torch.empty((bsz, k), dtype=torch.float64, device=dev) if want_clearance else None
-    traj_c = torch.empty((bsz,), dtype=torch.float64, device=dev) if want_clearance else None
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    cur = ctx._enter()
-    rc = ctx.lib.mtg_check_obstacle_clearance(ctx.handle, n, k, dim, bsz, ptr(coeffs), ptr(times), sb, sk, ptr(obstacles), m, osb,
-                                              float(inflation), ptr(feas), ptr(fseg), ptr(fobs), ptr(seg_c), ptr(seg_o), ptr(seg_t),
-                                              ptr(traj_c))
-    ctx._leave(cur)
-    _check(ctx.lib, rc, ctx.handle)
-    return ObstacleClearanceResult(feas, fseg, fobs, seg_c, seg_o, seg_t, traj_c)
-
-
-def check_obstacle_clearance_host(coeffs, times, obstacles, inflation: float = 0.0,
-                                  times_layout: str = "aos") -> ObstacleClearanceResult:
-    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
-    [B][K][D][N] or one trajectory [K][D][N] (then obstacles [M][4], results without the batch axis).  A radius that is
-    negative or not finite raises."""
-    lib = L.load()
-    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
-    times = np.ascontiguousarray(times, dtype=np.float64)
-    obstacles = np.ascontiguousarray(obstacles, dtype=np.float64)
-    single = coeffs.ndim == 3
-    if single:
-        coeffs, times = coeffs[None], times[None]
-    bsz, k, dim, n = coeffs.shape
-    if times.size != bsz * k:
-        raise MtgError(-1, "times must hold one value per segment")
-    m, osb = _obstacle_stride(obstacles.shape, bsz)
-    feas = np.empty((bsz,), dtype=np.int32)
-    fseg = np.empty((bsz,), dtype=np.int32)
-    fobs = np.empty((bsz,), dtype=np.int32)
-    seg_c = np.empty((bsz, k), dtype=np.float64)
-    seg_o = np.empty((bsz, k), dtype=np.int32)
-    seg_t = np.empty((bsz, k), dtype=np.float64)
-    traj_c = np.empty((bsz,), dtype=np.float64)
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    rc = lib.mtg_check_obstacle_clearance_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk, obstacles.ctypes.data,
-                                               m, osb, float(inflation), feas.ctypes.data, fseg.ctypes.data, fobs.ctypes.data,
-                                               seg_c.ctypes.data, seg_o.ctypes.data, seg_t.ctypes.data, traj_c.ctypes.data)
-    _check(lib, rc)
-    res = ObstacleClearanceResult(feas, fseg, fobs, seg_c, seg_o, seg_t, traj_c)
-    return ObstacleClearanceResult(*[a[0] for a in res]) if single else res
 
 
 class Plan:

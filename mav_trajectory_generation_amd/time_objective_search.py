@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib as L
 from .core import MtgError, Plan, _check
+from .segment_checks import magnitude_soft_cost, magnitude_soft_cost_host  # noqa: F401  (the maxima + soft-cost stage alone)
 
 MAX_MAGNITUDE_CONSTRAINTS = 4
 
@@ -102,54 +103,6 @@ def time_objective(plan: Plan, times, d_fixed, params: TimeObjectiveParams, d_fr
         plan.ctx._leave(cur)
     _check(plan.lib, rc, plan.ctx.handle)
     return TimeObjectiveResult(objective, components, maxima, violations, coeffs)
-
-
-def magnitude_soft_cost(ctx, coeffs, times, params: TimeObjectiveParams, times_layout: str = "aos"):
-    """The maxima + soft-cost stage alone (the third term of getTotalCostWithSoftConstraints): coeffs [B][K][D][N], times ([B][K]
-    'aos' / [K][B] 'soa') CUDA tensors -> (cost_soft [B], maxima [B][n_constraints], violations [B][n_constraints])."""
-    import torch
-    bsz, k, dim, n = coeffs.shape
-    assert coeffs.is_cuda and coeffs.dtype == torch.float64 and coeffs.is_contiguous() and times.is_contiguous()
-    nc = params.n_constraints
-    cost = torch.empty((bsz,), dtype=torch.float64, device=coeffs.device)
-    maxima = torch.empty((bsz, nc), dtype=torch.float64, device=coeffs.device)
-    violations = torch.empty((bsz, nc), dtype=torch.float64, device=coeffs.device)
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    c = params.to_c()
-    cur = ctx._enter()
-    rc = ctx.lib.mtg_magnitude_soft_cost(ctx.handle, n, k, dim, bsz, ctypes.c_void_p(coeffs.data_ptr()),
-                                         ctypes.c_void_p(times.data_ptr()), sb, sk, ctypes.byref(c), ctypes.c_void_p(cost.data_ptr()),
-                                         ctypes.c_void_p(maxima.data_ptr()) if nc else None,
-                                         ctypes.c_void_p(violations.data_ptr()) if nc else None)
-    ctx._leave(cur)
-    _check(ctx.lib, rc, ctx.handle)
-    return cost, maxima, violations
-
-
-def magnitude_soft_cost_host(coeffs, times, params: TimeObjectiveParams, times_layout: str = "aos"):
-    """The same on numpy arrays through the library's host build of the same lane code (no context, no device): coeffs
-    [B][K][D][N] or one trajectory [K][D][N]; returns numpy (cost_soft, maxima, violations)."""
-    lib = L.load()
-    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
-    times = np.ascontiguousarray(times, dtype=np.float64)
-    single = coeffs.ndim == 3
-    if single:
-        coeffs, times = coeffs[None], times[None]
-    bsz, k, dim, n = coeffs.shape
-    if times.size != bsz * k:
-        raise MtgError(-1, "times must hold one value per segment")
-    nc = params.n_constraints
-    cost = np.empty((bsz,), dtype=np.float64)
-    maxima = np.empty((bsz, nc), dtype=np.float64)
-    violations = np.empty((bsz, nc), dtype=np.float64)
-    sb, sk = (k, 1) if times_layout == "aos" else (1, bsz)
-    c = params.to_c()
-    rc = lib.mtg_magnitude_soft_cost_host(n, k, dim, bsz, coeffs.ctypes.data, times.ctypes.data, sb, sk, ctypes.byref(c),
-                                          cost.ctypes.data, maxima.ctypes.data, violations.ctypes.data)
-    _check(lib, rc)
-    if single:
-        return cost[0], maxima[0], violations[0]
-    return cost, maxima, violations
 
 
 def time_cost_host(times, params: TimeObjectiveParams):
