@@ -4,7 +4,8 @@
 // computeMaxVelocityAndAcceleration, scaleSegmentTimesToMeetConstraints (src/trajectory.cpp:81-141, :190-227,
 // :343-361, :385-429), and softConstraintCost -- the soft-constraint term of the time optimisers' objective
 // (PolynomialOptimizationNonLinear<N>::evaluateMaximumMagnitudeAsSoftConstraint), and checkObstacleClearance -- clearance from a set
-// of spheres, what a caller of the reference loops offsetTrajectory + computeMinMaxMagnitude for.  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
+// of spheres, what a caller of the reference loops offsetTrajectory + computeMinMaxMagnitude for, and checkKeepOutZones -- the same
+// question for convex zones (boxes, prisms) given as half spaces.  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
 // The single-trajectory functions stay on the host (trajectory.h); this class is for B >> 1.
 #ifndef MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
 #define MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
@@ -194,6 +195,45 @@ class TrajectoryBatch {
     return true;
   }
 
+  // Whether every trajectory stays OUTSIDE a set of convex keep-out zones (mtg_check_keep_out_zones): zones = M x n_planes x (nx, ny,
+  // nz, offset), unit normals pointing into the zone, offset = point . normal (the six planes of HalfPlane::createBoundingBox are a
+  // box), shared by all trajectories; inflation = the vehicle's radius.  feasible[b]: min over [0, T] of max_j (offset_j - n_j . p(t))
+  // - inflation > 0 for every zone and segment; first_segment / first_zone: the first failing segment and its smallest failing zone
+  // (-1: none); clearance[b]: the minimum itself (NaN wins).  The outputs are optional.  false: n_planes not in 1 .. 8, no or more
+  // than 4096 zones, D not 3 or 4, more than 2^19 - 1 segments, a negative or non-finite inflation.  Returns true when the check ran.
+  bool checkKeepOutZones(const std::vector<double>& zones, int n_planes, double inflation, std::vector<char>* feasible,
+                         std::vector<int>* first_segment = nullptr, std::vector<int>* first_zone = nullptr,
+                         std::vector<double>* clearance = nullptr) {
+    if (n_planes < 1 || n_planes > 8 || zones.size() % (4 * (size_t)n_planes) != 0) return false;
+    const size_t m = zones.size() / (4 * (size_t)n_planes);
+    if (m < 1 || m > 4096 || !(D_ == 3 || D_ == 4) || K_ >= (1 << 19)) return false;
+    if (!(inflation >= 0.0) || inflation > 1.7976931348623157e308) return false;
+    double* d_zones = (double*)dmalloc(sizeof(double) * zones.size());
+    check(mtg_copy_to_device(ctx(), d_zones, zones.data(), sizeof(double) * zones.size()));
+    int32_t* d_int = (int32_t*)dmalloc(sizeof(int32_t) * 3 * B_);
+    double* d_clear = (double*)dmalloc(sizeof(double) * B_);
+    check(mtg_check_keep_out_zones(ctx(), N_, K_, D_, B_, coeffs_, times_, K_, 1, d_zones, (int32_t)m, n_planes, 0, inflation, d_int,
+                                   d_int + B_, d_int + 2 * B_, nullptr, nullptr, nullptr, d_clear));
+    std::vector<int32_t> h(3 * B_);
+    check(mtg_copy_to_host(ctx(), h.data(), d_int, sizeof(int32_t) * h.size()));
+    if (clearance) {
+      clearance->resize(B_);
+      check(mtg_copy_to_host(ctx(), clearance->data(), d_clear, sizeof(double) * B_));
+    }
+    mtg_device_free(ctx(), d_zones);
+    mtg_device_free(ctx(), d_int);
+    mtg_device_free(ctx(), d_clear);
+    if (feasible) feasible->resize(B_);
+    if (first_segment) first_segment->resize(B_);
+    if (first_zone) first_zone->resize(B_);
+    for (int64_t b = 0; b < B_; ++b) {
+      if (feasible) (*feasible)[b] = (char)(h[b] != 0);
+      if (first_segment) (*first_segment)[b] = h[B_ + b];
+      if (first_zone) (*first_zone)[b] = h[2 * B_ + b];
+    }
+    return true;
+  }
+
   // In place on the device copy; returns true when every trajectory ended within range.
   bool scaleSegmentTimesToMeetConstraints(double v_max, double a_max, std::vector<char>* within_range = nullptr,
                                           std::vector<double>* scaling = nullptr) {
@@ -336,6 +376,42 @@ inline bool mtgCheckObstacleClearance(const Trajectory& trajectory, const std::v
   }
   if (first_segment) *first_segment = fseg;
   if (first_obstacle) *first_obstacle = fobs;
+  if (clearance) *clearance = lowest;
+  return feasible != 0;
+}
+
+// One trajectory against a set of convex keep-out zones on the HOST (mtg_check_keep_out_zones_host: no device, no context); an
+// addition of this library like the function above.  zones = M x n_planes x (nx, ny, nz, offset) as in
+// TrajectoryBatch::checkKeepOutZones.  Returns the verdict; first_segment / first_zone (-1: none) and clearance (the minimum over the
+// trajectory, NaN wins) are optional.  Arguments the check refuses (no zones, n_planes not in 1 .. 8, D not 3 or 4, a normal that is
+// not of unit length, an offset or inflation that is not finite, a negative inflation): false, with first_segment = first_zone = -1
+// and clearance NaN.
+inline bool mtgCheckKeepOutZones(const Trajectory& trajectory, const std::vector<double>& zones, int n_planes, double inflation = 0.0,
+                                 int* first_segment = nullptr, int* first_zone = nullptr, double* clearance = nullptr) {
+  const int n = trajectory.N(), k = trajectory.K(), dim = trajectory.D();
+  std::vector<double> c((size_t)k * dim * n), t((size_t)k);
+  for (int s = 0; s < k; ++s) {
+    const Segment& seg = trajectory.segments()[s];
+    t[s] = seg.getTime();
+    for (int d = 0; d < dim; ++d) {
+      const Eigen::VectorXd v = seg[d].getCoefficients();
+      for (int i = 0; i < n; ++i) c[((size_t)s * dim + d) * n + i] = v[i];
+    }
+  }
+  int32_t feasible = 0, fseg = -1, fzone = -1;
+  double lowest = 0.0;
+  const bool whole = n_planes >= 1 && n_planes <= 8 && zones.size() % (4 * (size_t)n_planes) == 0;
+  const int rc = !whole ? MTG_ERR_INVALID_ARGUMENT
+                        : mtg_check_keep_out_zones_host(n, k, dim, 1, c.data(), t.data(), k, 1, zones.data(),
+                                                        (int32_t)(zones.size() / (4 * (size_t)n_planes)), n_planes, 0, inflation, &feasible,
+                                                        &fseg, &fzone, nullptr, nullptr, nullptr, &lowest);
+  if (rc != MTG_OK) {
+    feasible = 0;
+    fseg = fzone = -1;
+    lowest = std::nan("");
+  }
+  if (first_segment) *first_segment = fseg;
+  if (first_zone) *first_zone = fzone;
   if (clearance) *clearance = lowest;
   return feasible != 0;
 }

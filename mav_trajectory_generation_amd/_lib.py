@@ -143,6 +143,10 @@ EXPORTS = {
     **_segment_entry("mtg_check_obstacle_clearance", [c_double_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
                                                       ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p, c_double_p,
                                                       c_double_p]),
+    **_segment_entry("mtg_check_keep_out_zones", [c_double_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p,
+                                                  c_double_p, c_double_p]),
+    "mtg_keep_out_boxes": (ctypes.c_int, [ctypes.c_int32, c_double_p, c_double_p, c_double_p]),
     "mtg_time_objective_params_init":(None, [ctypes.POINTER(TimeObjectiveParamsC)]),
     "mtg_time_objective": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Layout), c_double_p, c_double_p, c_double_p,
                                           ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p, c_double_p,

@@ -33,17 +33,9 @@ struct ObParams {
   int n_obstacles;
 };
 
-// unsigned order = numeric order, and NaN below every number (-infinity maps to 0x000f.., so 0 is free)
-__device__ unsigned long long order_key(double x) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  if (x != x) return 0ull;
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-constexpr unsigned long long kKeyInfinity = 0xfff0000000000000ull;   // order_key(+infinity): "no clearance yet"
-__device__ double order_value(unsigned long long k) {
-  if (k == 0ull) return NAN;
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
+using mtgs::kKeyInfinity;
+using mtgs::order_key;
+using mtgs::order_value;
 
 // SHARED: one obstacle set for every lane (stride 0) -- the set's address is a kernel argument and the scan's loads are scalar.
 template <int NC, bool SHARED>

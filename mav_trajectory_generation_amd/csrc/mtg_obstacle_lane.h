@@ -124,23 +124,14 @@ MTGX_HD void hull(const double (&c)[NC], bool nan, double& lo, double& hi) {
   hi = nan ? NAN : h;
 }
 
-template <int NC, class Roots>
-MTGX_HD void segment_prepare(const double* c, int N, int D, double T, Segment<NC>& S, Roots& roots) {
-  double p[3][NC], tpow[NC];
-  mtgs::load_padded(c, N, D, p);
+// the segment's four quarter boxes and E_dim from its padded coefficients p and tpow[i] = T^i (also the keep-out zone check's,
+// mtg_keepout_lane.h); c, N, D, T are recorded as they are
+template <int NC>
+MTGX_HD void segment_boxes(const double* c, int N, int D, double T, const double (&p)[3][NC], const double (&tpow)[NC], Segment<NC>& S) {
   S.c = c;
   S.N = N;
   S.D = D;
   S.T = T;
-  tpow[0] = 1.0;
-#pragma unroll
-  for (int i = 1; i < NC; ++i) tpow[i] = tpow[i - 1] * T;
-  {
-    double g0[2 * NC - 2];
-    mtgs::magnitude_derivative<NC, 3, 0, false>(p, nullptr, T, g0);
-#pragma unroll
-    for (int j = 0; j < 2 * NC - 2; ++j) roots[roots_len(NC) + j] = g0[j];
-  }
   constexpr int n = NC - 1;
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
@@ -167,6 +158,22 @@ MTGX_HD void segment_prepare(const double* c, int N, int D, double T, Segment<NC
     hull<NC>(q1, nan, S.lo[3][d], S.hi[3][d]);
     S.e[d] = e;
   }
+}
+
+template <int NC, class Roots>
+MTGX_HD void segment_prepare(const double* c, int N, int D, double T, Segment<NC>& S, Roots& roots) {
+  double p[3][NC], tpow[NC];
+  mtgs::load_padded(c, N, D, p);
+  tpow[0] = 1.0;
+#pragma unroll
+  for (int i = 1; i < NC; ++i) tpow[i] = tpow[i - 1] * T;
+  {
+    double g0[2 * NC - 2];
+    mtgs::magnitude_derivative<NC, 3, 0, false>(p, nullptr, T, g0);
+#pragma unroll
+    for (int j = 0; j < 2 * NC - 2; ++j) roots[roots_len(NC) + j] = g0[j];
+  }
+  segment_boxes<NC>(c, N, D, T, p, tpow, S);
 }
 
 // a lower bound on every clearance the evaluation computes for this obstacle over the segment (header comment); NaN if

@@ -59,6 +59,19 @@ __global__ void first_failure_init_kernel(int* word, Key* key, Key key_seed, lon
 // a failing lane: the atomic minimum keeps the first failure whichever lane finishes first
 __device__ __forceinline__ void report_failure(int* word, int segment, int code) { atomicMin(word, failure_word(segment, code)); }
 
+// A trajectory's minimum of a double through atomicMin on an unsigned word (the clearance checks): unsigned order = numeric
+// order, and NaN below every number (-infinity maps to 0x000f.., so 0 is free)
+__device__ __forceinline__ unsigned long long order_key(double x) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(x);
+  if (x != x) return 0ull;
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+constexpr unsigned long long kKeyInfinity = 0xfff0000000000000ull;   // order_key(+infinity): "no clearance yet"
+__device__ __forceinline__ double order_value(unsigned long long k) {
+  if (k == 0ull) return NAN;
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
 inline dim3 grid_for(long long lanes, int threads) { return dim3((unsigned)((lanes + threads - 1) / threads)); }
 
 // the context's stream, with its device made current

@@ -504,6 +504,76 @@ def check_obstacle_clearance_host(coeffs, times, obstacles, inflation: float = 0
     return _obstacle_clearance(_SegmentBatch.host(coeffs, times, times_layout), obstacles, inflation, True)
 
 
+def keep_out_boxes(centers, sizes) -> np.ndarray:
+    """n boxes as keep-out zones: centers [n][3] and sizes [n][3] (or one [3] for all) -> [n][6][4], bounding_box_half_planes per
+    box in its own plane order and signs.  A size that is not positive or not finite raises."""
+    lib = L.load()
+    centers = np.ascontiguousarray(centers, dtype=np.float64)
+    if centers.ndim != 2 or centers.shape[1] != 3:
+        raise MtgError(-1, "centers must be [n][3]")
+    try:
+        sizes = np.ascontiguousarray(np.broadcast_to(np.asarray(sizes, dtype=np.float64), centers.shape))
+    except ValueError:
+        raise MtgError(-1, "sizes must be [n][3] or [3]") from None
+    out = np.empty((centers.shape[0], 6, 4), dtype=np.float64)
+    _check(lib, lib.mtg_keep_out_boxes(centers.shape[0], centers.ctypes.data, sizes.ctypes.data, out.ctypes.data))
+    return out
+
+
+class KeepOutResult(NamedTuple):
+    """trajectory_feasible [B] int32 (1 / 0), first_failing_segment [B] int32 (-1: none), first_failing_zone [B] int32 (-1: none),
+    segment_clearance [B][K], segment_nearest_zone [B][K] int32, segment_closest_time [B][K], trajectory_clearance [B] (minimum
+    over t of max_j (offset_j - n_j . p(t)) - inflation; a NaN wins); the last four None if not asked for."""
+    trajectory_feasible: object
+    first_failing_segment: object
+    first_failing_zone: object
+    segment_clearance: object
+    segment_nearest_zone: object
+    segment_closest_time: object
+    trajectory_clearance: object
+
+
+def _zone_shape(shape, bsz: int):
+    """[P][4]: one zone; [M][P][4]: one set for every trajectory; [B][M][P][4]: a set per trajectory."""
+    if len(shape) not in (2, 3, 4) or shape[-1] != 4:
+        raise MtgError(-1, "zones must be [P][4], [M][P][4] or [B][M][P][4]")
+    p = int(shape[-2])
+    m = int(shape[-3]) if len(shape) >= 3 else 1
+    if len(shape) == 4 and shape[0] != bsz:
+        raise MtgError(-1, "zones: the batch axis must match coeffs")
+    return m, p, (4 * p * m if len(shape) == 4 else 0)
+
+
+def _keep_out_zones(b: _SegmentBatch, zones, inflation, want_clearance) -> KeepOutResult:
+    zones = b.extra(zones, "zones")
+    m, p, zsb = _zone_shape(tuple(zones.shape), b.B)
+    feas = b.empty((b.B,), b.i32)
+    fseg = b.empty((b.B,), b.i32)
+    fzone = b.empty((b.B,), b.i32)
+    seg_c = b.empty((b.B, b.K), b.f64, want_clearance)
+    seg_z = b.empty((b.B, b.K), b.i32, want_clearance)
+    seg_t = b.empty((b.B, b.K), b.f64, want_clearance)
+    traj_c = b.empty((b.B,), b.f64, want_clearance)
+    b.call("mtg_check_keep_out_zones", zones, m, p, zsb, float(inflation), feas, fseg, fzone, seg_c, seg_z, seg_t, traj_c)
+    return b.result((feas, fseg, fzone, seg_c, seg_z, seg_t, traj_c), KeepOutResult._make)
+
+
+def check_keep_out_zones(ctx: "Context", coeffs, times, zones, inflation: float = 0.0, times_layout: str = "aos",
+                         want_clearance: bool = True) -> KeepOutResult:
+    """Batched check that solved trajectories stay OUTSIDE a set of convex zones (boxes, prisms): coeffs [B][K][D][N] (D = 3 or
+    4), times ([B][K] 'aos' / [K][B] 'soa') and zones ([M][P][4] or [B][M][P][4] rows of (unit normal pointing into the zone,
+    offset), see keep_out_boxes; one [P][4] array, as bounding_box_half_planes returns it, is one zone) as CUDA float64 tensors.
+    A zone fails a segment iff not min_t max_j (offset_j - n_j . p(t)) - inflation > 0."""
+    return _keep_out_zones(_SegmentBatch.device(ctx, coeffs, times, times_layout), zones, inflation, want_clearance)
+
+
+def check_keep_out_zones_host(coeffs, times, zones, inflation: float = 0.0, times_layout: str = "aos") -> KeepOutResult:
+    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
+    [B][K][D][N] or one trajectory [K][D][N] (then zones [P][4] or [M][P][4], results without the batch axis).  A normal that
+    is not of unit length or an offset that is not finite raises."""
+    return _keep_out_zones(_SegmentBatch.host(coeffs, times, times_layout), zones, inflation, True)
+
+
 def _magnitude_soft_cost(b: _SegmentBatch, params):
     nc = params.n_constraints
     cost = b.empty((b.B,), b.f64)
