@@ -5,7 +5,8 @@
 // :343-361, :385-429), and softConstraintCost -- the soft-constraint term of the time optimisers' objective
 // (PolynomialOptimizationNonLinear<N>::evaluateMaximumMagnitudeAsSoftConstraint), and checkObstacleClearance -- clearance from a set
 // of spheres, what a caller of the reference loops offsetTrajectory + computeMinMaxMagnitude for, and checkKeepOutZones -- the same
-// question for convex zones (boxes, prisms) given as half spaces.  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
+// question for convex zones (boxes, prisms) given as half spaces, and checkDistanceField -- a sampled check against a voxel grid of
+// distances (an ESDF).  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
 // The single-trajectory functions stay on the host (trajectory.h); this class is for B >> 1.
 #ifndef MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
 #define MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
@@ -234,6 +235,38 @@ class TrajectoryBatch {
     return true;
   }
 
+  // Whether every trajectory is collision-free at every SAMPLE in a voxel grid of distances (mtg_check_distance_field; between
+  // samples nothing is certified): field.distances is a DEVICE pointer (DeviceDistanceField below uploads a host grid once), the rest
+  // of the struct is read on the host.  Every segment is sampled at local times 0, i dt < T and T; feasible[b]: distance(p(t)) -
+  // inflation > 0 at every sample of every segment, and no segment with more than max_samples samples; first_segment: the first
+  // failing segment (-1: none); clearance[b]: the minimum itself (NaN wins).  The outputs are optional.  false: arguments the check
+  // refuses (include/mtg_hip.h).  Returns true when the check ran, whatever the verdicts.
+  bool checkDistanceField(const mtg_distance_field& field, double dt, double inflation, std::vector<char>* feasible,
+                          std::vector<int>* first_segment = nullptr, std::vector<double>* clearance = nullptr, int max_samples = 4096) {
+    int32_t* d_int = (int32_t*)dmalloc(sizeof(int32_t) * 2 * B_);
+    double* d_clear = (double*)dmalloc(sizeof(double) * B_);
+    const int rc = mtg_check_distance_field(ctx(), N_, K_, D_, B_, coeffs_, times_, K_, 1, &field, dt, max_samples, inflation, d_int,
+                                            d_int + B_, nullptr, nullptr, nullptr, nullptr, d_clear);
+    if (rc == MTG_OK) {
+      std::vector<int32_t> h(2 * B_);
+      check(mtg_copy_to_host(ctx(), h.data(), d_int, sizeof(int32_t) * h.size()));
+      if (clearance) {
+        clearance->resize(B_);
+        check(mtg_copy_to_host(ctx(), clearance->data(), d_clear, sizeof(double) * B_));
+      }
+      if (feasible) feasible->resize(B_);
+      if (first_segment) first_segment->resize(B_);
+      for (int64_t b = 0; b < B_; ++b) {
+        if (feasible) (*feasible)[b] = (char)(h[b] != 0);
+        if (first_segment) (*first_segment)[b] = h[B_ + b];
+      }
+    }
+    mtg_device_free(ctx(), d_int);
+    mtg_device_free(ctx(), d_clear);
+    if (rc != MTG_OK && rc != MTG_ERR_INVALID_ARGUMENT) check(rc);
+    return rc == MTG_OK;
+  }
+
   // In place on the device copy; returns true when every trajectory ended within range.
   bool scaleSegmentTimesToMeetConstraints(double v_max, double a_max, std::vector<char>* within_range = nullptr,
                                           std::vector<double>* scaling = nullptr) {
@@ -412,6 +445,64 @@ inline bool mtgCheckKeepOutZones(const Trajectory& trajectory, const std::vector
   }
   if (first_segment) *first_segment = fseg;
   if (first_zone) *first_zone = fzone;
+  if (clearance) *clearance = lowest;
+  return feasible != 0;
+}
+
+// A voxel grid of distances on the device for TrajectoryBatch::checkDistanceField: the grid of a HOST mtg_distance_field is
+// uploaded once, field() is the same description with the device pointer.  Owns the device copy.
+class DeviceDistanceField {
+ public:
+  explicit DeviceDistanceField(const mtg_distance_field& host) : field_(host) {
+    const size_t bytes = sizeof(float) * (size_t)host.nx * (size_t)host.ny * (size_t)host.nz;
+    void* p = nullptr;
+    CHECK(host.distances != nullptr && host.nx > 0 && host.ny > 0 && host.nz > 0);
+    CHECK(mtg_device_malloc(mtg_compat_detail::context(), bytes, &p) == MTG_OK);
+    CHECK(mtg_copy_to_device(mtg_compat_detail::context(), p, host.distances, bytes) == MTG_OK);
+    field_.distances = (const float*)p;
+  }
+  DeviceDistanceField(const DeviceDistanceField&) = delete;
+  DeviceDistanceField& operator=(const DeviceDistanceField&) = delete;
+  ~DeviceDistanceField() { mtg_device_free(mtg_compat_detail::context(), (void*)field_.distances); }
+  const mtg_distance_field& field() const { return field_; }
+
+ private:
+  mtg_distance_field field_;
+};
+
+// One trajectory against a voxel grid of distances on the HOST (mtg_check_distance_field_host: no device, no context); an addition
+// of this library like the functions above.  field.distances is a host pointer.  A SAMPLED check: every segment at local times 0,
+// i dt < T and T.  Returns the verdict; first_segment (-1: none), first_time (the local time of the first failing sample of that
+// segment; NaN: none, or that segment has more than max_samples samples) and clearance (the minimum of distance - inflation over the
+// samples, NaN wins) are optional.  Arguments the check refuses (include/mtg_hip.h): false, with first_segment = -1, first_time and
+// clearance NaN.
+inline bool mtgCheckDistanceField(const Trajectory& trajectory, const mtg_distance_field& field, double dt, double inflation = 0.0,
+                                  int* first_segment = nullptr, double* first_time = nullptr, double* clearance = nullptr,
+                                  int max_samples = 4096) {
+  const int n = trajectory.N(), k = trajectory.K(), dim = trajectory.D();
+  std::vector<double> c((size_t)k * dim * n), t((size_t)k);
+  for (int s = 0; s < k; ++s) {
+    const Segment& seg = trajectory.segments()[s];
+    t[s] = seg.getTime();
+    for (int d = 0; d < dim; ++d) {
+      const Eigen::VectorXd v = seg[d].getCoefficients();
+      for (int i = 0; i < n; ++i) c[((size_t)s * dim + d) * n + i] = v[i];
+    }
+  }
+  int32_t feasible = 0, fseg = -1;
+  double lowest = 0.0, ftime = std::nan("");
+  std::vector<int32_t> failing((size_t)k), samples((size_t)k);
+  const int rc = mtg_check_distance_field_host(n, k, dim, 1, c.data(), t.data(), k, 1, &field, dt, max_samples, inflation, &feasible, &fseg,
+                                               nullptr, nullptr, failing.data(), samples.data(), &lowest);
+  if (rc != MTG_OK) {
+    feasible = 0;
+    fseg = -1;
+    lowest = std::nan("");
+  } else if (fseg >= 0 && failing[fseg] >= 0) {
+    ftime = failing[fseg] == samples[fseg] - 1 ? t[fseg] : (double)failing[fseg] * dt;
+  }
+  if (first_segment) *first_segment = fseg;
+  if (first_time) *first_time = ftime;
   if (clearance) *clearance = lowest;
   return feasible != 0;
 }

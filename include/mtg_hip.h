@@ -669,6 +669,75 @@ int mtg_check_keep_out_zones_host(int32_t n_coeffs, int32_t n_segments, int32_t 
  * own plane order and signs.  A size that is not positive or not finite is MTG_ERR_INVALID_ARGUMENT.  Host pointers. */
 int mtg_keep_out_boxes(int32_t n, const double* centers, const double* sizes, double* out);
 
+/* ---- next to the keep-out check: batched distance-field (ESDF voxel grid) clearance check ---------
+ * For planners whose map is a voxel grid of distances (a Euclidean signed distance field, an inflated occupancy map), not a
+ * list of shapes: which trajectories of a batch are collision-free in the map, where the others fail first, and by how much
+ * each segment misses.  Replaces mtg_sample_range followed by index arithmetic, a gather and a reduction by the caller.
+ * This is a SAMPLED check: between two samples nothing is certified.  The caller chooses dt against the vehicle's speed
+ * and the map's resolution (a sample spacing of v_max dt well below voxel_size, and an inflation that covers the rest).
+ * Everything below is float64 unless said otherwise, and every rule is fixed so that a host loop reproduces each choice.
+ *   samples      of a segment with time T: local times t_0 = 0, then t_i = fl(i dt) for every i >= 1 with fl(i dt) < T
+ *                (strict), then T itself as the last sample: S >= 2 of them, T never twice; T <= 0 or NaN: 0 and T.
+ *                Sample index S - 1 means local time T, any other index i means fl(i dt).  S is found without walking
+ *                (T / dt against max_samples as doubles, then one correction by the rule's own test).  If
+ *                S > max_samples the segment is NOT sampled: segment_samples -1, segment_clearance NaN, both sample
+ *                indices -1, and the segment fails.  That cap bounds the run time of a call.
+ *   position     Polynomial::evaluate's Horner form (one fused multiply-add per coefficient) over dimensions 0-2; a 4th
+ *                (yaw) dimension is never read
+ *   voxel coord  u_a = fl(fl(p_a - origin_a) r),  r = fl(1 / voxel_size), a = x, y, z
+ *   trilinear    inside iff 0 <= u_a <= n_a - 1 on every axis (closed); cell i_a = min((int)floor(u_a), n_a - 2) (a sample
+ *                exactly on the last centre uses f = 1), f_a = fl(u_a - i_a); the eight floats are converted to double
+ *                and combined along x, then y, then z, each step as fma(f, hi - lo, lo).  Needs n_a >= 2.
+ *   nearest      i_a = (int)floor(fl(u_a + 0.5)); inside iff 0 <= i_a <= n_a - 1.  Needs n_a >= 1.
+ *   outside      a sample outside the grid takes outside_distance; a NaN u_a gives a NaN; non-finite voxels follow from
+ *                the arithmetic above
+ *   clearance    of a sample: fl(d - inflation); the sample fails iff !(clearance > 0).  A NaN FAILS and wins every minimum
+ *                it enters (segment and trajectory), as in the sphere and zone checks.  There is no early exit.           */
+enum { MTG_FIELD_NEAREST = 0, MTG_FIELD_TRILINEAR = 1 };
+typedef struct mtg_distance_field {
+  const float* distances;      /* [nz][ny][nx], x fastest; device pointer (host pointer in the host form) */
+  int32_t nx, ny, nz;          /* each >= 2 (trilinear) or >= 1 (nearest); nx ny nz <= 2^31 - 1 */
+  double  origin[3];           /* position of the CENTRE of voxel (0,0,0); finite */
+  double  voxel_size;          /* h > 0, finite, 1 / h finite */
+  double  outside_distance;    /* value of a sample outside the grid; any double but NaN (0: unknown is an obstacle, +inf: free) */
+  int32_t interpolation;       /* MTG_FIELD_NEAREST 0, MTG_FIELD_TRILINEAR 1 */
+} mtg_distance_field;
+void mtg_distance_field_init(mtg_distance_field* field);   /* zeroes; trilinear; outside_distance 0 */
+/*   n_coeffs                 1 .. 12 (odd counts and counts below 4 run zero-padded in the next even instantiation)
+ *   n_segments               1 .. 2^19 - 1
+ *   dimension                3 or 4
+ *   times                    times[b * times_stride_b + k * times_stride_k]; strides >= 1, [B][K] or [K][B] without overlap
+ *   field                    read by the entry on the HOST; only field->distances is a device pointer
+ *   dt                       > 0 and finite
+ *   max_samples              2 .. 2^20: the largest S a segment may have
+ *   inflation                >= 0 and finite: the vehicle's radius
+ *   trajectory_feasible          out [batch]; required: 1 / 0
+ *   first_failing_segment        out optional [batch]: first failing segment in segment order, -1 if none
+ *   segment_clearance            out optional [batch][K]: minimum over all S samples
+ *   segment_closest_sample       out optional [batch][K]: smallest sample index that attains it; with a NaN the smallest
+ *                                index that produced one
+ *   segment_first_failing_sample out optional [batch][K]: smallest failing index, -1 if none
+ *   segment_samples              out optional [batch][K]: S, or -1 (not sampled)
+ *   trajectory_clearance         out optional [batch]: minimum over the segments
+ * Device pointers; asynchronous on the context's stream, three launches (init, segment kernel, per-trajectory decode), no
+ * workspace, capturable.  Argument errors (null required pointers, n_a out of range or more than 2^31 - 1 voxels, voxel_size,
+ * origin or inflation not finite or out of range, NaN outside_distance, unknown interpolation, bad dt or max_samples, a bad
+ * shape): MTG_ERR_INVALID_ARGUMENT, nothing enqueued; batch == 0 returns before anything is.  */
+int mtg_check_distance_field(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                             const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                             const mtg_distance_field* field, double dt, int32_t max_samples, double inflation,
+                             int32_t* trajectory_feasible, int32_t* first_failing_segment, double* segment_clearance,
+                             int32_t* segment_closest_sample, int32_t* segment_first_failing_sample,
+                             int32_t* segment_samples, double* trajectory_clearance);
+/* The same check with HOST pointers (field->distances too) on the library's host build of the same code, synchronous; needs
+ * no context and no device.  */
+int mtg_check_distance_field_host(int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                                  const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                                  const mtg_distance_field* field, double dt, int32_t max_samples, double inflation,
+                                  int32_t* trajectory_feasible, int32_t* first_failing_segment, double* segment_clearance,
+                                  int32_t* segment_closest_sample, int32_t* segment_first_failing_sample,
+                                  int32_t* segment_samples, double* trajectory_clearance);
+
 /* ---- the time optimisers' objective with soft constraints ---------------------------------------
  * Replaces, for a batch, the callbacks PolynomialOptimizationNonLinear<N> hands to nlopt
  * (impl/polynomial_optimization_nonlinear_impl.h, NL below): objectiveFunctionTime (NL:556-615) and

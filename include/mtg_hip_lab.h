@@ -24,6 +24,8 @@
  *   "sample_generic"   0 / 1                       mtg_sample_range never through its compile-time-shape kernels
  *   "sample_max_blocks" 0 default, >= 1            upper limit of the persistent grid (workgroups) of mtg_sample_range: a small launch
  *                      then runs every wave through several steps of its pipeline (tests/test_gpu_sampling.py)
+ *   "field_lanes"      0 default, 1 / 4 / 16 / 64  lanes that share one (trajectory, segment) of mtg_check_distance_field (anything
+ *                      else is 0); no output depends on it
  * Returns MTG_OK, or MTG_ERR_INVALID_ARGUMENT for an unknown name.                                                  */
 #ifndef MTG_HIP_LAB_H_
 #define MTG_HIP_LAB_H_

@@ -26,10 +26,12 @@ from .time_objective_search import PatternSearchResult, time_cost_host  # noqa: 
 # (PEP 562).  They are not bound at import: tests/test_segment_batch.py pins dir() of the package to the list it had when the
 # per-segment calls moved to segment_checks.py.
 _KEEP_OUT = ("keep_out_boxes", "check_keep_out_zones", "check_keep_out_zones_host", "KeepOutResult")
+# (the distance-field check likewise)
+_DISTANCE_FIELD = ("DistanceField", "DistanceFieldResult", "check_distance_field", "check_distance_field_host")
 
 
 def __getattr__(name):
-    if name in _KEEP_OUT:
+    if name in _KEEP_OUT or name in _DISTANCE_FIELD:
         from . import segment_checks
         return getattr(segment_checks, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

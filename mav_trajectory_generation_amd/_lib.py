@@ -44,6 +44,12 @@ class TimeObjectiveParamsC(ctypes.Structure):   # mtg_time_objective_params
                 ("derivative", ctypes.c_int32 * 4), ("value", ctypes.c_double * 4)]
 
 
+class DistanceFieldC(ctypes.Structure):   # mtg_distance_field
+    _fields_ = [("distances", ctypes.c_void_p), ("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32),
+                ("origin", ctypes.c_double * 3), ("voxel_size", ctypes.c_double), ("outside_distance", ctypes.c_double),
+                ("interpolation", ctypes.c_int32)]
+
+
 # what every per-segment entry (segment_checks.py) starts with: N, K, D, B, coeffs, times, times_stride_b, times_stride_k
 _SEGMENT = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64]
 
@@ -147,6 +153,10 @@ EXPORTS = {
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p,
                                                   c_double_p, c_double_p]),
     "mtg_keep_out_boxes": (ctypes.c_int, [ctypes.c_int32, c_double_p, c_double_p, c_double_p]),
+    "mtg_distance_field_init": (None, [ctypes.POINTER(DistanceFieldC)]),
+    **_segment_entry("mtg_check_distance_field", [ctypes.POINTER(DistanceFieldC), ctypes.c_double, ctypes.c_int32, ctypes.c_double,
+                                                  ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, c_double_p]),
     "mtg_time_objective_params_init":(None, [ctypes.POINTER(TimeObjectiveParamsC)]),
     "mtg_time_objective": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Layout), c_double_p, c_double_p, c_double_p,
                                           ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p, c_double_p,
@@ -177,6 +187,7 @@ ENV_OPTIONS = {
     "MTG_SAMPLE_MAX_BLOCKS": ("sample_max_blocks", int),
     "MTG_COOP": ("coop", int),
     "MTG_EXTREMA_SPLIT": ("extrema_split", int),
+    "MTG_FIELD_LANES": ("field_lanes", int),
 }
 
 FLAG_HOST_POINTERS = 1

@@ -110,14 +110,16 @@ int mtg_context_set_option(mtg_context* ctx, const char* name, int value) {
   else if (n == "sample_max_blocks") ctx->knob_sample_max_blocks = std::max(0, value);
   else if (n == "coop") ctx->knobs.coop = value;
   else if (n == "extrema_split") ctx->knob_extrema_split = value;
+  else if (n == "field_lanes") ctx->knob_field_lanes = (value == 1 || value == 4 || value == 16 || value == 64) ? value : 0;
   else return set_err(ctx, MTG_ERR_INVALID_ARGUMENT, "unknown option: " + n);
   return MTG_OK;
 }
 
-// (mtg_sample.hip, mtg_extrema.hip)
+// (mtg_sample.hip, mtg_extrema.hip, mtg_field.hip)
 bool mtg_context_sample_generic(const mtg_context* ctx) { return ctx && ctx->knob_sample_generic; }
 int mtg_context_sample_max_blocks(const mtg_context* ctx) { return ctx ? ctx->knob_sample_max_blocks : 0; }
 int mtg_context_extrema_split(const mtg_context* ctx) { return ctx ? ctx->knob_extrema_split : -1; }
+int mtg_context_field_lanes(const mtg_context* ctx) { return ctx ? ctx->knob_field_lanes : 0; }
 
 int mtg_context_destroy(mtg_context* ctx) {
   if (!ctx) return MTG_OK;

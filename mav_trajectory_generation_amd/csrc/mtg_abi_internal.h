@@ -44,6 +44,7 @@ struct mtg_context {
   bool knob_sample_generic = false;  // MTG_SAMPLE_GENERIC: mtg_sample_range never through its LDS-staged kernel
   int knob_sample_max_blocks = 0;    // MTG_SAMPLE_MAX_BLOCKS: >= 1 caps the persistent grid of mtg_sample_range (0: occupancy x CUs, the shipped grid)
   int knob_extrema_split = -1;       // MTG_EXTREMA_SPLIT: lanes per root search of the extrema kernels (include/mtg_hip_lab.h; -1: default)
+  int knob_field_lanes = 0;          // MTG_FIELD_LANES: lanes that share one segment of the distance-field check (1 / 4 / 16 / 64; 0: default)
   // MTG_FLAG_CONCURRENT_ITEMS requests: side streams (created on first use) + fork / join events
   std::vector<hipStream_t> side_streams;
   hipEvent_t fork_event = nullptr;

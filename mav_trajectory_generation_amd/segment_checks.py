@@ -1,5 +1,5 @@
 """The batched per-segment calls: everything that takes a solved batch `coeffs [B][K][D][N]` with strided `times` -- sampling,
-extrema, time scaling, the input-feasibility, half-plane and obstacle checks and the time objective's soft cost -- in the device
+extrema, time scaling, the input-feasibility, half-plane, obstacle and distance-field checks and the time objective's soft cost -- in the device
 form (CUDA tensors, a Context) and the host form (numpy, the library's host build of the same lane code).
 
 This is the Python half of the frame the C++ side has in csrc/mtg_segment_lane.h / mtg_segment_kernel.h: _SegmentBatch validates
@@ -93,12 +93,14 @@ class _SegmentBatch:
         """An uninitialised output next to coeffs (dtype: self.f64 / self.i32), or None if it is not wanted."""
         return self._new(shape, dtype=dtype) if want else None
 
-    def extra(self, x, what: str):
-        """A further float64 input (planes, obstacles, a workspace): validated on the device form, converted on the host form."""
+    def extra(self, x, what: str, dtype: str = "float64"):
+        """A further input of one dtype (planes, obstacles, a workspace: float64; a voxel grid: float32): validated on the device
+        form, converted on the host form."""
         if self.ctx is None:
-            return np.ascontiguousarray(x, dtype=np.float64)
-        if x.dtype is not self.f64:
-            _bad("%s must be a float64 tensor" % what)
+            return np.ascontiguousarray(x, dtype=dtype)
+        import torch
+        if x.dtype is not getattr(torch, dtype):
+            _bad("%s must be a %s tensor" % (what, dtype))
         if not x.is_contiguous():
             _bad("%s must be contiguous" % what)
         if x.device != self.coeffs.device:
@@ -572,6 +574,126 @@ def check_keep_out_zones_host(coeffs, times, zones, inflation: float = 0.0, time
     [B][K][D][N] or one trajectory [K][D][N] (then zones [P][4] or [M][P][4], results without the batch axis).  A normal that
     is not of unit length or an offset that is not finite raises."""
     return _keep_out_zones(_SegmentBatch.host(coeffs, times, times_layout), zones, inflation, True)
+
+
+_INTERPOLATION = {"nearest": 0, "trilinear": 1}
+
+
+class DistanceField:
+    """A voxel grid of distances (an ESDF, an inflated occupancy map): distances float32 [nz][ny][nx], x fastest (a CUDA tensor
+    for check_distance_field, a numpy array for check_distance_field_host), origin = position of the CENTRE of voxel (0, 0, 0),
+    voxel_size h > 0, outside_distance = the value of a sample outside the grid (0: unknown space is an obstacle, inf: free;
+    not NaN), interpolation 'trilinear' or 'nearest'."""
+    __slots__ = ("distances", "origin", "voxel_size", "outside_distance", "interpolation")
+
+    def __init__(self, distances, origin, voxel_size: float, outside_distance: float = 0.0, interpolation: str = "trilinear"):
+        try:
+            origin = tuple(float(x) for x in origin)
+        except TypeError:
+            origin = ()
+        if len(origin) != 3:
+            _bad("origin must hold 3 numbers")
+        if interpolation not in _INTERPOLATION:
+            _bad("interpolation must be 'trilinear' or 'nearest'")
+        self.distances, self.origin, self.voxel_size = distances, origin, float(voxel_size)
+        self.outside_distance, self.interpolation = float(outside_distance), interpolation
+
+    @classmethod
+    def from_corner(cls, distances, min_corner, voxel_size: float, outside_distance: float = 0.0, interpolation: str = "trilinear"):
+        """For maps whose origin is the lower CORNER of voxel (0, 0, 0): its centre is the corner plus h / 2 on every axis."""
+        try:
+            origin = [float(x) + 0.5 * float(voxel_size) for x in min_corner]
+        except TypeError:
+            origin = ()
+        return cls(distances, origin, voxel_size, outside_distance, interpolation)
+
+
+class DistanceFieldResult(NamedTuple):
+    """trajectory_feasible [B] int32 (1 / 0), first_failing_segment [B] int32 (-1: none), segment_clearance [B][K],
+    segment_closest_sample [B][K] int32, segment_first_failing_sample [B][K] int32 (-1: none), segment_samples [B][K] int32 (S;
+    -1: more than max_samples, not sampled), trajectory_clearance [B] (minimum over the samples of distance - inflation; a NaN
+    wins), and two times derived from them: segment_closest_time [B][K] (local time of the closest sample: T for sample S - 1,
+    else i dt; NaN if not sampled) and first_failing_time [B] (local time of the first failing sample of the first failing
+    segment; NaN for a feasible trajectory or a segment that was not sampled).  Everything per segment, and the two times, are
+    None if the segments were not asked for."""
+    trajectory_feasible: object
+    first_failing_segment: object
+    segment_clearance: object
+    segment_closest_sample: object
+    segment_first_failing_sample: object
+    segment_samples: object
+    trajectory_clearance: object
+    segment_closest_time: object
+    first_failing_time: object
+
+
+def _sample_times(b: _SegmentBatch, index, samples, times, dt):
+    """where(i == S - 1, T, i dt), NaN where i < 0, as operations on whole arrays of either form."""
+    if b.ctx is None:
+        return np.where(index < 0, np.nan, np.where(index == samples - 1, times, index * dt))
+    import torch
+    t = torch.where(index == samples - 1, times, index.to(times.dtype) * dt)
+    return torch.where(index < 0, torch.full_like(t, float("nan")), t)
+
+
+def _distance_field(b: _SegmentBatch, field, dt, inflation, max_samples, want_segments) -> DistanceFieldResult:
+    if not isinstance(field, DistanceField):
+        _bad("field must be a DistanceField")
+    grid = field.distances
+    if b.ctx is None and not isinstance(grid, np.ndarray):
+        _bad("distances must be a numpy array")
+    if b.ctx is not None and not isinstance(grid, b._kind):
+        _bad("distances must be a tensor")
+    if b.ctx is None and (grid.dtype != np.float32 or not grid.flags.c_contiguous):
+        _bad("distances must be a contiguous float32 array")
+    if len(grid.shape) != 3:
+        _bad("distances must be [nz][ny][nx]")
+    grid = b.extra(grid, "distances", "float32")
+    nz, ny, nx = (int(n) for n in grid.shape)
+    if nx * ny * nz == 0 or nx * ny * nz > 2**31 - 1:
+        _bad("distances must hold 1 .. 2^31 - 1 voxels")
+    c = L.DistanceFieldC(grid.ctypes.data if b.ctx is None else grid.data_ptr(), nx, ny, nz, (ctypes.c_double * 3)(*field.origin),
+                         field.voxel_size, field.outside_distance, _INTERPOLATION[field.interpolation])
+    feas = b.empty((b.B,), b.i32)
+    fseg = b.empty((b.B,), b.i32)
+    seg_c = b.empty((b.B, b.K), b.f64, want_segments)
+    seg_i = b.empty((b.B, b.K), b.i32, want_segments)
+    seg_f = b.empty((b.B, b.K), b.i32, want_segments)
+    seg_s = b.empty((b.B, b.K), b.i32, want_segments)
+    traj_c = b.empty((b.B,), b.f64)
+    b.call("mtg_check_distance_field", ctypes.byref(c), float(dt), int(max_samples), float(inflation), feas, fseg, seg_c, seg_i, seg_f,
+           seg_s, traj_c)
+    seg_t = fail_t = None
+    if want_segments:
+        times = b.times.reshape(b.B, b.K) if b._strides[1] == 1 else b.times.reshape(b.K, b.B).T
+        seg_t = _sample_times(b, seg_i, seg_s, times, float(dt))
+        k = fseg.clip(0)[:, None]
+        if b.ctx is None:
+            pick = lambda a: np.take_along_axis(a, k, 1)[:, 0]
+            fail_t = np.where(fseg < 0, np.nan, _sample_times(b, pick(seg_f), pick(seg_s), pick(times), float(dt)))
+        else:
+            import torch
+            pick = lambda a: torch.gather(a, 1, k.long())[:, 0]
+            fail_t = _sample_times(b, pick(seg_f), pick(seg_s), pick(times), float(dt))
+            fail_t = torch.where(fseg < 0, torch.full_like(fail_t, float("nan")), fail_t)
+    return b.result((feas, fseg, seg_c, seg_i, seg_f, seg_s, traj_c, seg_t, fail_t), DistanceFieldResult._make)
+
+
+def check_distance_field(ctx: "Context", coeffs, times, field: DistanceField, dt: float, inflation: float = 0.0, max_samples: int = 4096,
+                         times_layout: str = "aos", want_segments: bool = True) -> DistanceFieldResult:
+    """Batched SAMPLED collision check of solved trajectories against a voxel grid of distances: coeffs [B][K][D][N] (D = 3 or 4),
+    times ([B][K] 'aos' / [K][B] 'soa') as CUDA float64 tensors, field a DistanceField whose distances are a float32 CUDA tensor.
+    Every segment is sampled at local times 0, i dt < T and T; a sample fails iff not distance(p(t)) - inflation > 0.  A segment
+    with more than max_samples samples is not sampled and fails.  Between samples nothing is certified: choose dt against the
+    vehicle's speed and the map's resolution.  include/mtg_hip.h has every rule."""
+    return _distance_field(_SegmentBatch.device(ctx, coeffs, times, times_layout), field, dt, inflation, max_samples, want_segments)
+
+
+def check_distance_field_host(coeffs, times, field: DistanceField, dt: float, inflation: float = 0.0, max_samples: int = 4096,
+                              times_layout: str = "aos") -> DistanceFieldResult:
+    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
+    [B][K][D][N] or one trajectory [K][D][N] (results then without the batch axis); field.distances a float32 numpy array."""
+    return _distance_field(_SegmentBatch.host(coeffs, times, times_layout), field, dt, inflation, max_samples, True)
 
 
 def _magnitude_soft_cost(b: _SegmentBatch, params):
