@@ -6,7 +6,7 @@
 // (PolynomialOptimizationNonLinear<N>::evaluateMaximumMagnitudeAsSoftConstraint), and checkObstacleClearance -- clearance from a set
 // of spheres, what a caller of the reference loops offsetTrajectory + computeMinMaxMagnitude for, and checkKeepOutZones -- the same
 // question for convex zones (boxes, prisms) given as half spaces, and checkDistanceField -- a sampled check against a voxel grid of
-// distances (an ESDF).  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
+// distances (an ESDF), certifyDistanceField its certified form.  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
 // The single-trajectory functions stay on the host (trajectory.h); this class is for B >> 1.
 #ifndef MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
 #define MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
@@ -267,6 +267,42 @@ class TrajectoryBatch {
     return rc == MTG_OK;
   }
 
+  // The CERTIFIED form of checkDistanceField (mtg_certify_distance_field): a verdict for every instant of every segment.
+  // field.distances is a DEVICE pointer (DeviceDistanceField), the field trilinear, lipschitz a Lipschitz constant of its
+  // interpolant (mtg_distance_field_lipschitz_host on the host grid).  result[b]: MTG_FIELD_COLLIDES / FREE / UNDECIDED_DEPTH /
+  // UNDECIDED_BUDGET of the first segment that is not FREE (else FREE); first_segment: that segment (-1: none); lower_bound[b]: a
+  // guaranteed lower bound of the minimum of distance - inflation over the whole trajectory; sampled_clearance[b]: the lowest
+  // evaluated sample, an upper bound of it.  The outputs are optional.  false: arguments the check refuses (include/mtg_hip.h).
+  // Returns true when the check ran, whatever the verdicts.
+  bool certifyDistanceField(const mtg_distance_field& field, double lipschitz, double inflation, std::vector<int>* result,
+                            std::vector<int>* first_segment = nullptr, std::vector<double>* lower_bound = nullptr,
+                            std::vector<double>* sampled_clearance = nullptr, int min_depth = 4, int max_depth = 16,
+                            int max_frontier = 1024) {
+    int32_t* d_int = (int32_t*)dmalloc(sizeof(int32_t) * 2 * B_);
+    double* d_bound = (double*)dmalloc(sizeof(double) * 2 * B_);
+    const int rc = mtg_certify_distance_field(ctx(), N_, K_, D_, B_, coeffs_, times_, K_, 1, &field, lipschitz, min_depth, max_depth,
+                                              max_frontier, inflation, d_int, d_int + B_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                              nullptr, d_bound, d_bound + B_);
+    if (rc == MTG_OK) {
+      std::vector<int32_t> h(2 * B_);
+      check(mtg_copy_to_host(ctx(), h.data(), d_int, sizeof(int32_t) * h.size()));
+      if (lower_bound) {
+        lower_bound->resize(B_);
+        check(mtg_copy_to_host(ctx(), lower_bound->data(), d_bound, sizeof(double) * B_));
+      }
+      if (sampled_clearance) {
+        sampled_clearance->resize(B_);
+        check(mtg_copy_to_host(ctx(), sampled_clearance->data(), d_bound + B_, sizeof(double) * B_));
+      }
+      if (result) result->assign(h.begin(), h.begin() + B_);
+      if (first_segment) first_segment->assign(h.begin() + B_, h.end());
+    }
+    mtg_device_free(ctx(), d_int);
+    mtg_device_free(ctx(), d_bound);
+    if (rc != MTG_OK && rc != MTG_ERR_INVALID_ARGUMENT) check(rc);
+    return rc == MTG_OK;
+  }
+
   // In place on the device copy; returns true when every trajectory ended within range.
   bool scaleSegmentTimesToMeetConstraints(double v_max, double a_max, std::vector<char>* within_range = nullptr,
                                           std::vector<double>* scaling = nullptr) {
@@ -505,6 +541,49 @@ inline bool mtgCheckDistanceField(const Trajectory& trajectory, const mtg_distan
   if (first_time) *first_time = ftime;
   if (clearance) *clearance = lowest;
   return feasible != 0;
+}
+
+// One trajectory against a trilinear voxel grid of distances on the HOST, CERTIFIED (mtg_certify_distance_field_host: no device, no
+// context): a verdict for every instant.  lipschitz <= 0: computed from the grid (mtg_distance_field_lipschitz_host).  Returns the
+// result code (MTG_FIELD_COLLIDES 0, MTG_FIELD_FREE 1, MTG_FIELD_UNDECIDED_DEPTH 2, MTG_FIELD_UNDECIDED_BUDGET 3) of the first
+// segment that is not FREE; first_segment (-1: none), first_time (the local time of the first failing sample of that segment; NaN:
+// none), lower_bound (guaranteed, of the minimum of distance - inflation) and sampled_clearance (the lowest sample) are optional.
+// Arguments the check refuses (include/mtg_hip.h): -1, with first_segment = -1 and the three values NaN.
+inline int mtgCertifyDistanceField(const Trajectory& trajectory, const mtg_distance_field& field, double lipschitz = 0.0,
+                                   double inflation = 0.0, int* first_segment = nullptr, double* first_time = nullptr,
+                                   double* lower_bound = nullptr, double* sampled_clearance = nullptr, int min_depth = 4, int max_depth = 16,
+                                   int max_frontier = 1024) {
+  const int n = trajectory.N(), k = trajectory.K(), dim = trajectory.D();
+  std::vector<double> c((size_t)k * dim * n), t((size_t)k);
+  for (int s = 0; s < k; ++s) {
+    const Segment& seg = trajectory.segments()[s];
+    t[s] = seg.getTime();
+    for (int d = 0; d < dim; ++d) {
+      const Eigen::VectorXd v = seg[d].getCoefficients();
+      for (int i = 0; i < n; ++i) c[((size_t)s * dim + d) * n + i] = v[i];
+    }
+  }
+  int32_t result = -1, fseg = -1;
+  double lower = std::nan(""), sampled = std::nan(""), ftime = std::nan("");
+  std::vector<double> failing((size_t)k);
+  int rc = MTG_OK;
+  if (!(lipschitz > 0.0)) rc = mtg_distance_field_lipschitz_host(&field, &lipschitz);
+  if (rc == MTG_OK)
+    rc = mtg_certify_distance_field_host(n, k, dim, 1, c.data(), t.data(), k, 1, &field, lipschitz, min_depth, max_depth, max_frontier,
+                                         inflation, &result, &fseg, nullptr, nullptr, nullptr, nullptr, failing.data(), nullptr, nullptr,
+                                         &lower, &sampled);
+  if (rc != MTG_OK) {
+    result = -1;
+    fseg = -1;
+    lower = sampled = std::nan("");
+  } else if (fseg >= 0) {
+    ftime = failing[fseg];
+  }
+  if (first_segment) *first_segment = fseg;
+  if (first_time) *first_time = ftime;
+  if (lower_bound) *lower_bound = lower;
+  if (sampled_clearance) *sampled_clearance = sampled;
+  return result;
 }
 
 }  // namespace mav_trajectory_generation

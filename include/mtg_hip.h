@@ -738,6 +738,83 @@ int mtg_check_distance_field_host(int32_t n_coeffs, int32_t n_segments, int32_t 
                                   int32_t* segment_closest_sample, int32_t* segment_first_failing_sample,
                                   int32_t* segment_samples, double* trajectory_clearance);
 
+/* ---- next to the sampled check: CERTIFIED distance-field check -----------------------------------
+ * A verdict for every instant of every segment, and a guaranteed lower bound of the minimum clearance next to the sampled
+ * upper bound: an adaptive interval bisection in which a node is one sample plus a Lipschitz bound of the field over the
+ * Taylor reach of the position around the sample.  Takes what mtg_check_distance_field takes except dt and max_samples, and
+ *   lipschitz L   the caller's promise: finite, > 0, and |D(x) - D(y)| <= L ||x - y|| for the trilinear interpolant D and all
+ *                 x, y inside the grid.  mtg_distance_field_lipschitz_host computes a rigorous one.  Trilinear fields only.
+ *   min_depth     0 .. 10, max_depth  min_depth .. 24, max_frontier  max(2, 2^min_depth) .. 1024
+ * Every step is fixed so that a host loop reproduces each choice; s = 2^-36, r = fl(1 / voxel_size), and every operation
+ * written below rounds once (no contraction) unless it is an fma.  A segment runs in the even instantiation NC of the sampled
+ * check (N zero-padded to 4, 6, .. 12); N below is that NC.
+ *   nodes      a segment with time T > 0 is covered by a binary tree; node (d, j), 0 <= j < 2^d, has half-width
+ *              w = T 2^-(d+1) (an exact scaling) and midpoint m = fl((2 j + 1) w).  The tree starts with all 2^min_depth nodes
+ *              of depth min_depth.  !(T > 0): ONE node with w = 0 and m = 0 (NaN T: m = T); it is terminal whatever its bound,
+ *              and segment_depth is 0.
+ *   per node   1. shift: q_a = the coefficients of axis a; for i = 0 .. N-2: for j = N-2 down to i: q[j] = fma(m, q[j+1], q[j]).
+ *                 Then q_a,0 = p_a(m) -- the sampled check's Horner value bit for bit -- and q_a,k = p_a^(k)(m) / k!.
+ *              2. reach: t = |q_a,N-1|; for k = N-2 .. 1: t = fma(t, w, |q_a,k|); R_a = t w  >= max_{|e| <= w} |p_a(m+e) - p_a(m)|
+ *                 (the Taylor bound: exact in real arithmetic, first-order tight for small w).
+ *              3. scale: A_a = horner over |c_a,N-1| .. |c_a,0| in |m| with one fma per coefficient, + |origin_a|.
+ *              4. Rh_a = fma(s, A_a, R_a (1 + s)),  Rh = sqrt(fma(Rh_z, Rh_z, fma(Rh_y, Rh_y, Rh_x Rh_x))) (1 + s).
+ *              5. sample: c = lookup(p(m)) - inflation with the sampled check's lookup (outside rule, NaN); fails iff !(c > 0).
+ *              6. box: u_a by the sampled check's rule, rho_a = (Rh_a r) (1 + s).  INSIDE iff 0 <= u_a - rho_a and
+ *                 u_a + rho_a <= n_a - 1 on every axis; TOUCHES iff u_a + rho_a >= 0 and u_a - rho_a <= n_a - 1 on every axis.
+ *                 A NaN among the u_a - rho_a and u_a + rho_a (a NaN position, an infinite reach): the bound is NaN.
+ *              7. bound_in: touches: Dc - inflation - L Rh - s (|Dc| + inflation + 2 L / r), left to right, Dc = the lookup
+ *                 at u clamped to [0, n_a - 1] per axis (the projection onto the convex grid is non-expansive: the clamped
+ *                 point certifies every point of the box that lies inside the grid); else +infinity.
+ *              8. bound_out: inside: +infinity; else outside_distance - inflation.
+ *              9. bound = min(bound_in, bound_out); a NaN wins.
+ *             10. fate: the sample fails: terminal, evidence of a collision; else bound > 0: terminal, certified; else
+ *                 d == max_depth (or the lone node): terminal, undecided; else replaced by its two children.
+ *   levels     breadth-first, a frontier in ascending j.  After a level, if the next frontier would hold more than
+ *              max_frontier nodes the segment stops with MTG_FIELD_UNDECIDED_BUDGET and its lower bound is -infinity.  The
+ *              budget and the depth limit bound a call's run time; there is no early exit.
+ *   segment    segment_result: 0 some evaluated sample failed (a definite point of the trajectory), 1 every terminal node is
+ *              certified, 2 / 3 undecided; 0 wins over 2 and 3, 3 over 2.  segment_lower_bound: min of bound over the terminal
+ *              nodes, a guaranteed lower bound of min_t D(p(t)) - inflation whatever the verdict; a NaN wins.
+ *              segment_sampled_clearance: min of c over all evaluated nodes (an upper bound of the true minimum; a NaN wins),
+ *              segment_closest_time the m of that node, ties to the smaller m.  segment_first_failing_time: the smallest m of
+ *              a failing sample, NaN if none.  segment_nodes: evaluated nodes; segment_depth: the deepest level evaluated.
+ *   trajectory trajectory_result: the code of the first segment, in segment order, that is not FREE, else 1;
+ *              first_failing_segment: that segment, -1 if none; the two bounds: minima over the segments.  A
+ *              trajectory_sampled_clearance <= 0 or NaN means that a definite collision exists somewhere.
+ * All outputs are minima, sums or maxima over a node set fixed by the rule: they do not depend on how nodes are spread over
+ * lanes, and the device and host forms agree bit for bit.  DESIGN.md 4.15 has the soundness argument.                      */
+enum { MTG_FIELD_COLLIDES = 0, MTG_FIELD_FREE = 1, MTG_FIELD_UNDECIDED_DEPTH = 2, MTG_FIELD_UNDECIDED_BUDGET = 3 };
+/* Device pointers; trajectory_result [batch] is required, every other output optional: first_failing_segment [batch] int32,
+ * segment_result / segment_nodes / segment_depth [batch][K] int32, segment_lower_bound / segment_sampled_clearance /
+ * segment_closest_time / segment_first_failing_time [batch][K], trajectory_lower_bound / trajectory_sampled_clearance [batch].
+ * Asynchronous on the context's stream, three launches (init, segment kernel: one 64-lane workgroup per segment, decode), no
+ * workspace, capturable.  Argument errors (those of the sampled check; a nearest field; lipschitz not finite and positive;
+ * the three ranges above): MTG_ERR_INVALID_ARGUMENT, nothing enqueued; batch == 0 returns before anything is.  */
+int mtg_certify_distance_field(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                               const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                               const mtg_distance_field* field, double lipschitz, int32_t min_depth, int32_t max_depth,
+                               int32_t max_frontier, double inflation, int32_t* trajectory_result,
+                               int32_t* first_failing_segment, int32_t* segment_result, double* segment_lower_bound,
+                               double* segment_sampled_clearance, double* segment_closest_time,
+                               double* segment_first_failing_time, int32_t* segment_nodes, int32_t* segment_depth,
+                               double* trajectory_lower_bound, double* trajectory_sampled_clearance);
+/* The same check with HOST pointers (field->distances too) on the library's host build of the same code, synchronous; needs
+ * no context and no device.  */
+int mtg_certify_distance_field_host(int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                                    const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                                    const mtg_distance_field* field, double lipschitz, int32_t min_depth, int32_t max_depth,
+                                    int32_t max_frontier, double inflation, int32_t* trajectory_result,
+                                    int32_t* first_failing_segment, int32_t* segment_result, double* segment_lower_bound,
+                                    double* segment_sampled_clearance, double* segment_closest_time,
+                                    double* segment_first_failing_time, int32_t* segment_nodes, int32_t* segment_depth,
+                                    double* trajectory_lower_bound, double* trajectory_sampled_clearance);
+/* A rigorous Lipschitz constant of the trilinear interpolant of a grid in HOST memory: per cell the largest absolute
+ * difference over its four x-edges, four y-edges and four z-edges, gx, gy, gz; out = max over the cells of
+ * sqrt(gx^2 + gy^2 + gz^2) / voxel_size, rounded up (times 1 + 2^-50).  Inside a cell dD/dx is a convex combination of the four
+ * x-edge differences over h, and the grid is convex, so the bound holds globally.  A non-finite voxel makes it non-finite
+ * (which the check refuses).  Reads distances, nx, ny, nz (each >= 2) and voxel_size only.  */
+int mtg_distance_field_lipschitz_host(const mtg_distance_field* field, double* out);
+
 /* ---- the time optimisers' objective with soft constraints ---------------------------------------
  * Replaces, for a batch, the callbacks PolynomialOptimizationNonLinear<N> hands to nlopt
  * (impl/polynomial_optimization_nonlinear_impl.h, NL below): objectiveFunctionTime (NL:556-615) and

@@ -28,10 +28,12 @@ from .time_objective_search import PatternSearchResult, time_cost_host  # noqa: 
 _KEEP_OUT = ("keep_out_boxes", "check_keep_out_zones", "check_keep_out_zones_host", "KeepOutResult")
 # (the distance-field check likewise)
 _DISTANCE_FIELD = ("DistanceField", "DistanceFieldResult", "check_distance_field", "check_distance_field_host")
+# (and the certified distance-field check)
+_CERTIFIED_FIELD = ("CertifiedFieldResult", "certify_distance_field", "certify_distance_field_host")
 
 
 def __getattr__(name):
-    if name in _KEEP_OUT or name in _DISTANCE_FIELD:
+    if name in _KEEP_OUT or name in _DISTANCE_FIELD or name in _CERTIFIED_FIELD:
         from . import segment_checks
         return getattr(segment_checks, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

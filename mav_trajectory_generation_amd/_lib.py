@@ -157,6 +157,11 @@ EXPORTS = {
     **_segment_entry("mtg_check_distance_field", [ctypes.POINTER(DistanceFieldC), ctypes.c_double, ctypes.c_int32, ctypes.c_double,
                                                   ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, c_double_p]),
+    **_segment_entry("mtg_certify_distance_field", [ctypes.POINTER(DistanceFieldC), ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    c_double_p, c_double_p]),
+    "mtg_distance_field_lipschitz_host": (ctypes.c_int, [ctypes.POINTER(DistanceFieldC), ctypes.POINTER(ctypes.c_double)]),
     "mtg_time_objective_params_init":(None, [ctypes.POINTER(TimeObjectiveParamsC)]),
     "mtg_time_objective": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Layout), c_double_p, c_double_p, c_double_p,
                                           ctypes.POINTER(TimeObjectiveParamsC), c_double_p, c_double_p, c_double_p, c_double_p,

@@ -87,11 +87,14 @@ MTGX_HD double sample_time(int i, int S, double T, double dt) { return i == S - 
 
 MTGX_HD void load2(const float* p, float (&v)[2]) { __builtin_memcpy(v, p, 2 * sizeof(float)); }   // the two x-neighbours at once
 
-// the field's value at position p (dimensions 0-2)
-MTGX_HD double lookup(const Grid& g, const double (&p)[3]) {
-  double u[3];
+// voxel coordinates of position p (dimensions 0-2)
+MTGX_HD void voxel_coordinates(const Grid& g, const double (&p)[3], double (&u)[3]) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) u[a] = (p[a] - g.o[a]) * g.r;
+}
+
+// the field's value at voxel coordinates u (the certified check, mtg_certify_lane.h, looks up clamped coordinates too)
+MTGX_HD double lookup_voxel(const Grid& g, const double (&u)[3]) {
   if (u[0] != u[0] || u[1] != u[1] || u[2] != u[2]) return NAN;
   const int n[3] = {g.nx, g.ny, g.nz};
   if (g.trilinear) {
@@ -131,6 +134,13 @@ MTGX_HD double lookup(const Grid& g, const double (&p)[3]) {
   }
   if (!inside) return g.outside;
   return (double)g.d[((long long)(int)v[2] * g.ny + (int)v[1]) * (long long)g.nx + (int)v[0]];
+}
+
+// the field's value at position p (dimensions 0-2)
+MTGX_HD double lookup(const Grid& g, const double (&p)[3]) {
+  double u[3];
+  voxel_coordinates(g, p, u);
+  return lookup_voxel(g, u);
 }
 
 // order_key of mtg_segment_kernel.h for host and device: unsigned order = numeric order, NaN below every number

@@ -607,6 +607,36 @@ class DistanceField:
             origin = ()
         return cls(distances, origin, voxel_size, outside_distance, interpolation)
 
+    def lipschitz_bound(self) -> float:
+        """A rigorous Lipschitz constant of the trilinear interpolant, the `lipschitz` of certify_distance_field: per cell the
+        largest absolute difference over its four x-, y- and z-edges (gx, gy, gz), then the maximum over the cells of
+        sqrt(gx^2 + gy^2 + gz^2) / h, rounded up.  A numpy grid goes through the library's host function; a CUDA tensor through
+        the same formula as torch operations in float64, times 1 + 2^-40.  Non-finite if a voxel is."""
+        grid = self.distances
+        if len(grid.shape) != 3 or min(int(n) for n in grid.shape) < 2:
+            _bad("distances must be [nz][ny][nx] with every axis >= 2")
+        if isinstance(grid, np.ndarray):
+            if grid.dtype != np.float32 or not grid.flags.c_contiguous:
+                _bad("distances must be a contiguous float32 array")
+            lib = L.load()
+            nz, ny, nx = (int(n) for n in grid.shape)
+            c = L.DistanceFieldC(grid.ctypes.data, nx, ny, nz, (ctypes.c_double * 3)(*self.origin), self.voxel_size,
+                                 self.outside_distance, _INTERPOLATION[self.interpolation])
+            out = ctypes.c_double()
+            _check(lib, lib.mtg_distance_field_lipschitz_host(ctypes.byref(c), ctypes.byref(out)))
+            return out.value
+        import torch
+        if not (self.voxel_size > 0.0):
+            _bad("voxel_size must be > 0")
+        g = grid.to(torch.float64)
+        dx, dy, dz = (g[:, :, 1:] - g[:, :, :-1]).abs(), (g[:, 1:, :] - g[:, :-1, :]).abs(), (g[1:, :, :] - g[:-1, :, :]).abs()
+        # the four parallel edges of a cell: the maximum over the two neighbours along each of the other two axes
+        gx = torch.maximum(torch.maximum(dx[:-1, :-1], dx[:-1, 1:]), torch.maximum(dx[1:, :-1], dx[1:, 1:]))
+        gy = torch.maximum(torch.maximum(dy[:-1, :, :-1], dy[:-1, :, 1:]), torch.maximum(dy[1:, :, :-1], dy[1:, :, 1:]))
+        gz = torch.maximum(torch.maximum(dz[:, :-1, :-1], dz[:, :-1, 1:]), torch.maximum(dz[:, 1:, :-1], dz[:, 1:, 1:]))
+        worst = torch.sqrt(gx * gx + gy * gy + gz * gz).amax()       # (torch.maximum and amax propagate a NaN)
+        return float(worst) / self.voxel_size * (1.0 + 2.0 ** -40)
+
 
 class DistanceFieldResult(NamedTuple):
     """trajectory_feasible [B] int32 (1 / 0), first_failing_segment [B] int32 (-1: none), segment_clearance [B][K],
@@ -636,7 +666,8 @@ def _sample_times(b: _SegmentBatch, index, samples, times, dt):
     return torch.where(index < 0, torch.full_like(t, float("nan")), t)
 
 
-def _distance_field(b: _SegmentBatch, field, dt, inflation, max_samples, want_segments) -> DistanceFieldResult:
+def _field_struct(b: _SegmentBatch, field):
+    """(grid, the mtg_distance_field of a DistanceField) for either form; grid keeps the voxels alive during the call."""
     if not isinstance(field, DistanceField):
         _bad("field must be a DistanceField")
     grid = field.distances
@@ -652,8 +683,12 @@ def _distance_field(b: _SegmentBatch, field, dt, inflation, max_samples, want_se
     nz, ny, nx = (int(n) for n in grid.shape)
     if nx * ny * nz == 0 or nx * ny * nz > 2**31 - 1:
         _bad("distances must hold 1 .. 2^31 - 1 voxels")
-    c = L.DistanceFieldC(grid.ctypes.data if b.ctx is None else grid.data_ptr(), nx, ny, nz, (ctypes.c_double * 3)(*field.origin),
-                         field.voxel_size, field.outside_distance, _INTERPOLATION[field.interpolation])
+    return grid, L.DistanceFieldC(grid.ctypes.data if b.ctx is None else grid.data_ptr(), nx, ny, nz, (ctypes.c_double * 3)(*field.origin),
+                                  field.voxel_size, field.outside_distance, _INTERPOLATION[field.interpolation])
+
+
+def _distance_field(b: _SegmentBatch, field, dt, inflation, max_samples, want_segments) -> DistanceFieldResult:
+    grid, c = _field_struct(b, field)
     feas = b.empty((b.B,), b.i32)
     fseg = b.empty((b.B,), b.i32)
     seg_c = b.empty((b.B, b.K), b.f64, want_segments)
@@ -694,6 +729,71 @@ def check_distance_field_host(coeffs, times, field: DistanceField, dt: float, in
     """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
     [B][K][D][N] or one trajectory [K][D][N] (results then without the batch axis); field.distances a float32 numpy array."""
     return _distance_field(_SegmentBatch.host(coeffs, times, times_layout), field, dt, inflation, max_samples, True)
+
+
+class CertifiedFieldResult(NamedTuple):
+    """trajectory_result [B] int32 (0 COLLIDES, 1 FREE, 2 UNDECIDED_DEPTH, 3 UNDECIDED_BUDGET: the code of the first segment that is
+    not FREE), first_failing_segment [B] int32 (-1: none), segment_result [B][K] int32, segment_lower_bound [B][K] (guaranteed
+    lower bound of min_t distance - inflation), segment_sampled_clearance [B][K] (its upper bound: the lowest sample),
+    segment_closest_time [B][K] (local time of that sample), segment_first_failing_time [B][K] (NaN: none), segment_nodes [B][K]
+    int32, segment_depth [B][K] int32, trajectory_lower_bound [B], trajectory_sampled_clearance [B], lipschitz (the constant the
+    call used).  Everything per segment is None if the segments were not asked for."""
+    trajectory_result: object
+    first_failing_segment: object
+    segment_result: object
+    segment_lower_bound: object
+    segment_sampled_clearance: object
+    segment_closest_time: object
+    segment_first_failing_time: object
+    segment_nodes: object
+    segment_depth: object
+    trajectory_lower_bound: object
+    trajectory_sampled_clearance: object
+    lipschitz: object
+
+
+def _certify_distance_field(b: _SegmentBatch, field, lipschitz, inflation, min_depth, max_depth, max_frontier,
+                            want_segments) -> CertifiedFieldResult:
+    grid, c = _field_struct(b, field)
+    if lipschitz is None:
+        lipschitz = field.lipschitz_bound()
+    res = b.empty((b.B,), b.i32)
+    fseg = b.empty((b.B,), b.i32)
+    seg_r = b.empty((b.B, b.K), b.i32, want_segments)
+    seg_l = b.empty((b.B, b.K), b.f64, want_segments)
+    seg_c = b.empty((b.B, b.K), b.f64, want_segments)
+    seg_t = b.empty((b.B, b.K), b.f64, want_segments)
+    seg_f = b.empty((b.B, b.K), b.f64, want_segments)
+    seg_n = b.empty((b.B, b.K), b.i32, want_segments)
+    seg_d = b.empty((b.B, b.K), b.i32, want_segments)
+    traj_l = b.empty((b.B,), b.f64)
+    traj_c = b.empty((b.B,), b.f64)
+    b.call("mtg_certify_distance_field", ctypes.byref(c), float(lipschitz), int(min_depth), int(max_depth), int(max_frontier),
+           float(inflation), res, fseg, seg_r, seg_l, seg_c, seg_t, seg_f, seg_n, seg_d, traj_l, traj_c)
+    r = b.result((res, fseg, seg_r, seg_l, seg_c, seg_t, seg_f, seg_n, seg_d, traj_l, traj_c))
+    return CertifiedFieldResult(*r, float(lipschitz))
+
+
+def certify_distance_field(ctx: "Context", coeffs, times, field: DistanceField, lipschitz: Optional[float] = None, inflation: float = 0.0,
+                           min_depth: int = 4, max_depth: int = 16, max_frontier: int = 1024, times_layout: str = "aos",
+                           want_segments: bool = True) -> CertifiedFieldResult:
+    """Batched CERTIFIED collision check of solved trajectories against a trilinear voxel grid of distances: coeffs [B][K][D][N]
+    (D = 3 or 4), times ([B][K] 'aos' / [K][B] 'soa') as CUDA float64 tensors, field a DistanceField whose distances are a float32
+    CUDA tensor.  Every segment is covered by an adaptive bisection of its time interval; a node is a sample at its midpoint plus
+    the bound distance - inflation - lipschitz * reach over the whole node.  A verdict holds for every instant: FREE is proven,
+    COLLIDES has a definite failing sample, the two UNDECIDED codes name the limit that stopped the search.  lipschitz=None
+    computes field.lipschitz_bound().  include/mtg_hip.h has every rule."""
+    return _certify_distance_field(_SegmentBatch.device(ctx, coeffs, times, times_layout), field, lipschitz, inflation, min_depth,
+                                   max_depth, max_frontier, want_segments)
+
+
+def certify_distance_field_host(coeffs, times, field: DistanceField, lipschitz: Optional[float] = None, inflation: float = 0.0,
+                                min_depth: int = 4, max_depth: int = 16, max_frontier: int = 1024,
+                                times_layout: str = "aos") -> CertifiedFieldResult:
+    """The same check on numpy arrays through the library's host build of the same code (no context, no device): coeffs
+    [B][K][D][N] or one trajectory [K][D][N] (results then without the batch axis); field.distances a float32 numpy array."""
+    return _certify_distance_field(_SegmentBatch.host(coeffs, times, times_layout), field, lipschitz, inflation, min_depth, max_depth,
+                                   max_frontier, True)
 
 
 def _magnitude_soft_cost(b: _SegmentBatch, params):
