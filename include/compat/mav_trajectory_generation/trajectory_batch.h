@@ -4,7 +4,8 @@
 // computeMaxVelocityAndAcceleration, scaleSegmentTimesToMeetConstraints (src/trajectory.cpp:81-141, :190-227,
 // :343-361, :385-429), and softConstraintCost -- the soft-constraint term of the time optimisers' objective
 // (PolynomialOptimizationNonLinear<N>::evaluateMaximumMagnitudeAsSoftConstraint), and checkObstacleClearance -- clearance from a set
-// of spheres, what a caller of the reference loops offsetTrajectory + computeMinMaxMagnitude for, and checkKeepOutZones -- the same
+// of spheres, what a caller of the reference loops offsetTrajectory + computeMinMaxMagnitude for, checkSeparation -- the distance
+// between pairs of trajectories over the time both fly, and checkKeepOutZones -- the same
 // question for convex zones (boxes, prisms) given as half spaces, and checkDistanceField -- a sampled check against a voxel grid of
 // distances (an ESDF), certifyDistanceField its certified form.  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
 // The single-trajectory functions stay on the host (trajectory.h); this class is for B >> 1.
@@ -192,6 +193,62 @@ class TrajectoryBatch {
       if (feasible) (*feasible)[b] = (char)(h[b] != 0);
       if (first_segment) (*first_segment)[b] = h[B_ + b];
       if (first_obstacle) (*first_obstacle)[b] = h[2 * B_ + b];
+    }
+    return true;
+  }
+
+  // Separation of trajectories of this batch (side A) from trajectories of `other` (side B, possibly this batch itself)
+  // (mtg_check_trajectory_separation): pairs = P x (index into this batch, index into other); start_a / start_b = the global time at
+  // which each trajectory starts (empty: 0); min_separation = the required centre-to-centre distance.  feasible[p]:
+  // ||pA(t) - pB(t)|| - min_separation > 0 at every instant both fly (a pair that never flies at the same time is feasible with
+  // separation +inf); first_segment_a / _b: the earliest failing piece (-1: none); separation[p]: the minimum itself (NaN wins);
+  // closest_time[p]: its GLOBAL time (NaN: none).  A pair with an index out of range, a negative or non-finite segment time or a
+  // non-finite start is infeasible with NaN separation.  The outputs are optional.  false: the two batches differ in N or D, D not 3
+  // or 4, more than 1024 segments on a side, pairs.size() odd, a start vector of the wrong size, a negative or non-finite
+  // min_separation.  Returns true when the check ran, whatever the verdicts.
+  bool checkSeparation(const TrajectoryBatch& other, const std::vector<int32_t>& pairs, double min_separation,
+                       const std::vector<double>& start_a, const std::vector<double>& start_b, std::vector<char>* feasible,
+                       std::vector<int>* first_segment_a = nullptr, std::vector<int>* first_segment_b = nullptr,
+                       std::vector<double>* separation = nullptr, std::vector<double>* closest_time = nullptr) {
+    const int64_t P = (int64_t)(pairs.size() / 2);
+    if (pairs.size() % 2 != 0 || other.N_ != N_ || other.D_ != D_ || !(D_ == 3 || D_ == 4) || K_ > 1024 || other.K_ > 1024) return false;
+    if ((!start_a.empty() && (int64_t)start_a.size() != B_) || (!start_b.empty() && (int64_t)start_b.size() != other.B_)) return false;
+    if (!(min_separation >= 0.0) || min_separation > 1.7976931348623157e308 || P > 0x7fffffffll / K_) return false;
+    if (feasible) feasible->resize(P);
+    if (first_segment_a) first_segment_a->resize(P);
+    if (first_segment_b) first_segment_b->resize(P);
+    if (separation) separation->resize(P);
+    if (closest_time) closest_time->resize(P);
+    if (P == 0) return true;
+    auto to_device = [&](const void* src, size_t bytes) {
+      void* d = dmalloc(bytes);
+      check(mtg_copy_to_device(ctx(), d, src, bytes));
+      return d;
+    };
+    double* d_sa = start_a.empty() ? nullptr : (double*)to_device(start_a.data(), sizeof(double) * start_a.size());
+    double* d_sb = start_b.empty() ? nullptr : (double*)to_device(start_b.data(), sizeof(double) * start_b.size());
+    int32_t* d_pairs = (int32_t*)to_device(pairs.data(), sizeof(int32_t) * pairs.size());
+    int32_t* d_int = (int32_t*)dmalloc(sizeof(int32_t) * (5 + 2 * K_) * P);      // feasible, first a, first b, closest a, closest b, 2 x [P][K]
+    double* d_dbl = (double*)dmalloc(sizeof(double) * (2 + 2 * K_) * P);         // separation, closest time, 2 x [P][K]
+    check(mtg_check_trajectory_separation(ctx(), N_, D_, K_, B_, coeffs_, times_, K_, 1, d_sa, other.K_, other.B_, other.coeffs_, other.times_,
+                                          other.K_, 1, d_sb, P, d_pairs, min_separation, d_int, d_int + P, d_int + 2 * P, d_dbl, d_dbl + P,
+                                          d_int + 3 * P, d_int + 4 * P, d_dbl + 2 * P, d_dbl + (2 + K_) * P, d_int + 5 * P,
+                                          d_int + (5 + K_) * P));
+    std::vector<int32_t> h(3 * P);
+    std::vector<double> hd(2 * P);
+    check(mtg_copy_to_host(ctx(), h.data(), d_int, sizeof(int32_t) * h.size()));
+    check(mtg_copy_to_host(ctx(), hd.data(), d_dbl, sizeof(double) * hd.size()));
+    if (d_sa) mtg_device_free(ctx(), d_sa);
+    if (d_sb) mtg_device_free(ctx(), d_sb);
+    mtg_device_free(ctx(), d_pairs);
+    mtg_device_free(ctx(), d_int);
+    mtg_device_free(ctx(), d_dbl);
+    for (int64_t p = 0; p < P; ++p) {
+      if (feasible) (*feasible)[p] = (char)(h[p] != 0);
+      if (first_segment_a) (*first_segment_a)[p] = h[P + p];
+      if (first_segment_b) (*first_segment_b)[p] = h[2 * P + p];
+      if (separation) (*separation)[p] = hd[p];
+      if (closest_time) (*closest_time)[p] = hd[P + p];
     }
     return true;
   }
@@ -446,6 +503,55 @@ inline bool mtgCheckObstacleClearance(const Trajectory& trajectory, const std::v
   if (first_segment) *first_segment = fseg;
   if (first_obstacle) *first_obstacle = fobs;
   if (clearance) *clearance = lowest;
+  return feasible != 0;
+}
+
+// Two trajectories against each other on the HOST (mtg_check_trajectory_separation_host: no device, no context); an addition of this
+// library like the function above.  start_a / start_b: the global time at which each starts.  Returns the verdict: true iff
+// ||a(t) - b(t)|| - min_separation > 0 at every instant both fly (two trajectories that never fly at the same time are apart).
+// first_segment_a / _b (the earliest failing piece, -1: none), separation (the minimum, +inf without a common instant, NaN wins) and
+// closest_time (its GLOBAL time, NaN: none) are optional.  Arguments the check refuses (different N or D, D not 3 or 4, more than
+// 1024 segments, a negative or non-finite min_separation): false, with the indices -1 and separation and closest_time NaN.
+inline bool mtgCheckTrajectorySeparation(const Trajectory& a, const Trajectory& b, double min_separation, double start_a = 0.0,
+                                         double start_b = 0.0, int* first_segment_a = nullptr, int* first_segment_b = nullptr,
+                                         double* separation = nullptr, double* closest_time = nullptr) {
+  const int n = a.N(), dim = a.D();
+  auto flat = [&](const Trajectory& trajectory, std::vector<double>& c, std::vector<double>& t) {
+    const int k = trajectory.K();
+    c.resize((size_t)k * dim * n);
+    t.resize((size_t)k);
+    for (int s = 0; s < k; ++s) {
+      const Segment& seg = trajectory.segments()[s];
+      t[s] = seg.getTime();
+      for (int d = 0; d < dim; ++d) {
+        const Eigen::VectorXd v = seg[d].getCoefficients();
+        for (int i = 0; i < n; ++i) c[((size_t)s * dim + d) * n + i] = v[i];
+      }
+    }
+  };
+  int32_t feasible = 0, fa = -1, fb = -1, ca = -1, cb = -1;
+  double lowest = 0.0, when = 0.0;
+  int rc = MTG_ERR_INVALID_ARGUMENT;
+  if (b.N() == n && b.D() == dim && a.K() >= 1 && b.K() >= 1) {
+    std::vector<double> c_a, t_a, c_b, t_b;
+    flat(a, c_a, t_a);
+    flat(b, c_b, t_b);
+    const int32_t pair[2] = {0, 0};
+    std::vector<double> seg_sep((size_t)a.K()), seg_time((size_t)a.K());
+    std::vector<int32_t> seg_b((size_t)a.K());
+    rc = mtg_check_trajectory_separation_host(n, dim, a.K(), 1, c_a.data(), t_a.data(), a.K(), 1, &start_a, b.K(), 1, c_b.data(), t_b.data(),
+                                              b.K(), 1, &start_b, 1, pair, min_separation, &feasible, &fa, &fb, &lowest, &when, &ca, &cb,
+                                              seg_sep.data(), seg_time.data(), seg_b.data(), nullptr);
+  }
+  if (rc != MTG_OK) {
+    feasible = 0;
+    fa = fb = -1;
+    lowest = when = std::nan("");
+  }
+  if (first_segment_a) *first_segment_a = fa;
+  if (first_segment_b) *first_segment_b = fb;
+  if (separation) *separation = lowest;
+  if (closest_time) *closest_time = when;
   return feasible != 0;
 }
 

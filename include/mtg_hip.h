@@ -608,6 +608,85 @@ int mtg_check_obstacle_clearance_host(int32_t n_coeffs, int32_t n_segments, int3
                                       double* segment_clearance, int32_t* segment_nearest_obstacle,
                                       double* segment_closest_time, double* trajectory_clearance);
 
+/* ---- next to the sphere check: batched trajectory-to-trajectory separation check ------------------
+ * Which pairs of solved trajectories keep a centre-to-centre distance above min_separation at every instant both fly,
+ * where the others first come too close, and the exact minimum distance of each pair.  Replaces sampling both
+ * trajectories and taking norms (which certifies nothing between samples), or a host loop over
+ * Segment::computeMinMaxMagnitudeCandidates on difference segments the caller would have to build.
+ * Side A is coeffs_a [batch_a][n_segments_a][dimension][n_coeffs] with its times and an optional global start time per
+ * trajectory; side B likewise with its own batch and segment count.  The two sides may be the same buffers.
+ *   Breakpoints  ea[0] = start_a (0 if start_a is null), ea[i + 1] = ea[i] + Ta[i]: one rounded float64 addition per
+ *                step, in segment order; eb likewise.
+ *   Pieces       all (i, j) with lo = max(ea[i], eb[j]) < hi = min(ea[i + 1], eb[j + 1]); along a pair they are ordered
+ *                in time, i + j increases strictly, there are at most Ka + Kb - 1.  On a piece sa = lo - ea[i],
+ *                sb = lo - eb[j], L = hi - lo and d(tau) = pA_i(sa + tau L) - pB_j(sb + tau L), tau in [0, 1].
+ *   Candidates   tau = 0 and tau = 1 exactly, and the real roots in [0, 1] of g = sum_dim d_dim d_dim', isolated directly
+ *                as in mtg_minmax_magnitude.  separation = || d(tau) || - min_separation over dimensions 0-2 (a 4th, yaw,
+ *                dimension is never read); a piece fails iff a candidate has !(separation > 0).
+ *   Fold         within a piece the candidates are taken in the order 0, 1, roots ascending with strict <, the first NaN
+ *                wins; across the pieces of a pair the earliest piece wins a tie and a NaN wins every minimum it enters
+ *                (the earliest one stays); the first failing piece is the earliest in time.  Times are global:
+ *                lo + tau L.  This is a safety check: a NaN separation FAILS.
+ *   No piece     (the two never fly at the same time, or touch at an instant only): the pair is feasible, its separation
+ *                +inf, its times NaN, its segment indices -1, its piece counts 0.  A vehicle that has landed occupies
+ *                nothing: a caller who wants it to keep its end point appends a constant segment.
+ *   Invalid pair a segment time that is negative or not finite, or a start that is not finite, on either side; or a pair
+ *                index outside [0, batch_a) x [0, batch_b), for which nothing of either side is read: the pair is
+ *                infeasible, its separations and times NaN, its segment indices -1, its piece counts 0.
+ *   n_coeffs                  1 .. 12 (odd counts and counts below 4 run zero-padded in the next even instantiation)
+ *   dimension                 3 or 4, shared by both sides
+ *   n_segments_a, _b          1 .. 1024 each
+ *   batch_a, batch_b          >= 0
+ *   times_a                   times_a[b * times_a_stride_b + k * times_a_stride_k]; strides >= 1, [B][K] or [K][B]
+ *                             without overlap; a segment of time 0 makes no piece.  times_b likewise
+ *   start_a, start_b          optional [batch]: the global time at which each trajectory starts; null: 0
+ *   n_pairs                   >= 0, n_pairs * n_segments_a < 2^31
+ *   pairs                     [n_pairs][2] int32: (index into A, index into B)
+ *   min_separation            >= 0 and finite: the required centre-to-centre distance (the sum of both radii)
+ *   pair_feasible             out [n_pairs]; required: 1 / 0
+ *   first_failing_segment_a   out optional [n_pairs]: segment of A of the earliest failing piece, -1 if none
+ *   first_failing_segment_b   out optional [n_pairs]: segment of B of that piece, -1 if none
+ *   pair_separation           out optional [n_pairs]: minimum over all pieces and candidates (no early exit)
+ *   pair_closest_time         out optional [n_pairs]: global time of the candidate that attains it
+ *   pair_closest_segment_a    out optional [n_pairs]: segment of A of that piece
+ *   pair_closest_segment_b    out optional [n_pairs]: segment of B of that piece
+ *   segment_separation        out optional [n_pairs][Ka]: minimum over the pieces of segment i of A; +inf without a piece
+ *   segment_closest_time      out optional [n_pairs][Ka]: global time of that candidate; NaN without a piece.  As for
+ *                             the extremum times of mtg_minmax_magnitude the VALUE is second order in the root's error,
+ *                             the TIME is not
+ *   segment_closest_segment_b out optional [n_pairs][Ka]: segment of B of that piece; -1 without a piece
+ *   segment_pieces            out optional [n_pairs][Ka]: pieces of segment i of A (pruned or not)
+ * Any of the three pair_closest outputs needs segment_separation, segment_closest_time and segment_closest_segment_b:
+ * they are found by a scan of those.  A piece is searched only if a lower bound of its separation from the hulls of the
+ * two sides' Bernstein control points on the piece (less a rounding allowance) is not both > 0 and above the running
+ * minimum of its segment of A: no result depends on the pruning.
+ * Device pointers (the pair indices are verified per pair, see above); asynchronous on the context's stream, three
+ * launches, no workspace, capturable.  Argument errors: MTG_ERR_INVALID_ARGUMENT, nothing enqueued; n_pairs == 0 returns
+ * before anything is.  The arguments are checked before the context is looked at (a null context is refused after
+ * them), so the argument rules can be exercised in a process without a device.  */
+int mtg_check_trajectory_separation(mtg_context* ctx, int32_t n_coeffs, int32_t dimension, int32_t n_segments_a, int64_t batch_a,
+                                    const double* coeffs_a, const double* times_a, int64_t times_a_stride_b,
+                                    int64_t times_a_stride_k, const double* start_a, int32_t n_segments_b, int64_t batch_b,
+                                    const double* coeffs_b, const double* times_b, int64_t times_b_stride_b,
+                                    int64_t times_b_stride_k, const double* start_b, int64_t n_pairs, const int32_t* pairs,
+                                    double min_separation, int32_t* pair_feasible, int32_t* first_failing_segment_a,
+                                    int32_t* first_failing_segment_b, double* pair_separation, double* pair_closest_time,
+                                    int32_t* pair_closest_segment_a, int32_t* pair_closest_segment_b,
+                                    double* segment_separation, double* segment_closest_time,
+                                    int32_t* segment_closest_segment_b, int32_t* segment_pieces);
+/* The same check with HOST pointers on the library's host build of the same code, synchronous; needs no context and
+ * no device.  Here the pair list is readable: an index outside its side's batch is MTG_ERR_INVALID_ARGUMENT.  */
+int mtg_check_trajectory_separation_host(int32_t n_coeffs, int32_t dimension, int32_t n_segments_a, int64_t batch_a,
+                                         const double* coeffs_a, const double* times_a, int64_t times_a_stride_b,
+                                         int64_t times_a_stride_k, const double* start_a, int32_t n_segments_b, int64_t batch_b,
+                                         const double* coeffs_b, const double* times_b, int64_t times_b_stride_b,
+                                         int64_t times_b_stride_k, const double* start_b, int64_t n_pairs, const int32_t* pairs,
+                                         double min_separation, int32_t* pair_feasible, int32_t* first_failing_segment_a,
+                                         int32_t* first_failing_segment_b, double* pair_separation, double* pair_closest_time,
+                                         int32_t* pair_closest_segment_a, int32_t* pair_closest_segment_b,
+                                         double* segment_separation, double* segment_closest_time,
+                                         int32_t* segment_closest_segment_b, int32_t* segment_pieces);
+
 /* ---- next to the sphere check: batched keep-out zone check (convex obstacles: boxes, prisms) ------
  * The complement of mtg_check_half_plane_feasibility: which trajectories stay OUTSIDE every zone of a set, where the
  * others enter first, and by how much each segment misses.  Replaces wrapping each box in a sphere, or a host loop.

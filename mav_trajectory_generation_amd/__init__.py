@@ -30,10 +30,12 @@ _KEEP_OUT = ("keep_out_boxes", "check_keep_out_zones", "check_keep_out_zones_hos
 _DISTANCE_FIELD = ("DistanceField", "DistanceFieldResult", "check_distance_field", "check_distance_field_host")
 # (and the certified distance-field check)
 _CERTIFIED_FIELD = ("CertifiedFieldResult", "certify_distance_field", "certify_distance_field_host")
+# (and the trajectory-to-trajectory separation check)
+_SEPARATION = ("TrajectorySeparationResult", "check_trajectory_separation", "check_trajectory_separation_host", "all_pairs")
 
 
 def __getattr__(name):
-    if name in _KEEP_OUT or name in _DISTANCE_FIELD or name in _CERTIFIED_FIELD:
+    if name in _KEEP_OUT or name in _DISTANCE_FIELD or name in _CERTIFIED_FIELD or name in _SEPARATION:
         from . import segment_checks
         return getattr(segment_checks, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

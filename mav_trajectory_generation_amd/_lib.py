@@ -63,6 +63,17 @@ def _segment_entry(name, tail, host=True):
     return entry
 
 
+def _separation_entry():
+    """mtg_check_trajectory_separation and its host twin: two sides (K, B, coeffs, times, two strides, start), the pair list, the
+    required distance and eleven outputs."""
+    side = [ctypes.c_int32, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int64, ctypes.c_int64, c_double_p]
+    tail = ([ctypes.c_int32, ctypes.c_int32] + side + side + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_double]
+            + [ctypes.c_void_p] * 3 + [c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_void_p,
+                                       ctypes.c_void_p])
+    return {"mtg_check_trajectory_separation": (ctypes.c_int, [ctypes.c_void_p] + tail),
+            "mtg_check_trajectory_separation_host": (ctypes.c_int, tail)}
+
+
 EXPORTS = {
     "mtg_context_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "mtg_context_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -152,6 +163,7 @@ EXPORTS = {
     **_segment_entry("mtg_check_keep_out_zones", [c_double_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double_p, ctypes.c_void_p,
                                                   c_double_p, c_double_p]),
+    **_separation_entry(),
     "mtg_keep_out_boxes": (ctypes.c_int, [ctypes.c_int32, c_double_p, c_double_p, c_double_p]),
     "mtg_distance_field_init": (None, [ctypes.POINTER(DistanceFieldC)]),
     **_segment_entry("mtg_check_distance_field", [ctypes.POINTER(DistanceFieldC), ctypes.c_double, ctypes.c_int32, ctypes.c_double,

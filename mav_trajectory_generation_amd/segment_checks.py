@@ -1,5 +1,5 @@
 """The batched per-segment calls: everything that takes a solved batch `coeffs [B][K][D][N]` with strided `times` -- sampling,
-extrema, time scaling, the input-feasibility, half-plane, obstacle and distance-field checks and the time objective's soft cost -- in the device
+extrema, time scaling, the input-feasibility, half-plane, obstacle, separation and distance-field checks and the time objective's soft cost -- in the device
 form (CUDA tensors, a Context) and the host form (numpy, the library's host build of the same lane code).
 
 This is the Python half of the frame the C++ side has in csrc/mtg_segment_lane.h / mtg_segment_kernel.h: _SegmentBatch validates
@@ -504,6 +504,99 @@ def check_obstacle_clearance_host(coeffs, times, obstacles, inflation: float = 0
     [B][K][D][N] or one trajectory [K][D][N] (then obstacles [M][4], results without the batch axis).  A radius that is
     negative or not finite raises."""
     return _obstacle_clearance(_SegmentBatch.host(coeffs, times, times_layout), obstacles, inflation, True)
+
+
+class TrajectorySeparationResult(NamedTuple):
+    """pair_feasible [P] int32 (1 / 0), first_failing_segment_a / _b [P] int32 (the earliest failing piece, -1: none),
+    pair_separation [P] (minimum over the common flight time of ||pA(t) - pB(t)|| - min_separation; +inf if the two never fly at the
+    same time, a NaN wins), pair_closest_time [P] (GLOBAL time of that minimum, NaN: none), pair_closest_segment_a / _b [P] int32,
+    and per segment of A: segment_separation [P][Ka], segment_closest_time [P][Ka], segment_closest_segment_b [P][Ka] int32,
+    segment_pieces [P][Ka] int32 (the pieces between merged breakpoints the segment was cut into).  The last seven are None if
+    the closest approach was not asked for."""
+    pair_feasible: object
+    first_failing_segment_a: object
+    first_failing_segment_b: object
+    pair_separation: object
+    pair_closest_time: object
+    pair_closest_segment_a: object
+    pair_closest_segment_b: object
+    segment_separation: object
+    segment_closest_time: object
+    segment_closest_segment_b: object
+    segment_pieces: object
+
+
+def all_pairs(n: int) -> np.ndarray:
+    """Every unordered pair of n trajectories: [n (n - 1) / 2][2] int32 rows (i, j) with i < j, in lexicographic order -- the pair
+    list of a swarm checked against itself."""
+    i, j = np.triu_indices(int(n), 1)
+    return np.ascontiguousarray(np.stack([i, j], axis=1).astype(np.int32))
+
+
+def _trajectory_separation(a: _SegmentBatch, b: _SegmentBatch, pairs, min_separation, start_a, start_b,
+                           want_closest) -> TrajectorySeparationResult:
+    if a.single or b.single:
+        _bad("coeffs must be [B][K][D][N] on both sides")
+    if (a.N, a.D) != (b.N, b.D):
+        _bad("both sides must have the same dimension and number of coefficients")
+    if a.ctx is not None and b.coeffs.device != a.coeffs.device:
+        _bad("both sides must be on the same device")
+    starts = []
+    for side, start, what in ((a, start_a, "start_a"), (b, start_b, "start_b")):
+        if start is not None:
+            start = a.extra(start, what)
+            if tuple(start.shape) != (side.B,):
+                _bad("%s must hold one start time per trajectory (%d)" % (what, side.B))
+        starts.append(start)
+    pairs = a.extra(pairs, "pairs", "int32")
+    if len(pairs.shape) != 2 or pairs.shape[1] != 2:
+        _bad("pairs must be [P][2]")
+    n = int(pairs.shape[0])
+    out = [a.empty((n,), a.i32), a.empty((n,), a.i32), a.empty((n,), a.i32), a.empty((n,), a.f64), a.empty((n,), a.f64, want_closest),
+           a.empty((n,), a.i32, want_closest), a.empty((n,), a.i32, want_closest), a.empty((n, a.K), a.f64, want_closest),
+           a.empty((n, a.K), a.f64, want_closest), a.empty((n, a.K), a.i32, want_closest), a.empty((n, a.K), a.i32, want_closest)]
+    ctx = a.ctx
+    if ctx is None:
+        addr = lambda x: None if x is None else _address(x)
+    else:
+        addr = lambda x: None if x is None else x.data_ptr()
+    args = [a.N, a.D]
+    for side, start in zip((a, b), starts):
+        args += [side.K, side.B, addr(side.coeffs), addr(side.times), *side._strides, addr(start)]
+    args += [n, addr(pairs), float(min_separation)] + [addr(x) for x in out]
+    if ctx is None:
+        lib = L.load()
+        _check(lib, lib.mtg_check_trajectory_separation_host(*args))
+    else:
+        cur = ctx._enter()
+        try:
+            rc = ctx.lib.mtg_check_trajectory_separation(ctx.handle, *args)
+        finally:
+            ctx._leave(cur)
+        _check(ctx.lib, rc, ctx.handle)
+    return TrajectorySeparationResult._make(out)
+
+
+def check_trajectory_separation(ctx: "Context", coeffs_a, times_a, coeffs_b, times_b, pairs, min_separation: float, start_a=None,
+                                start_b=None, times_layout: str = "aos", want_closest: bool = True) -> TrajectorySeparationResult:
+    """Batched separation of solved trajectories from EACH OTHER: side A coeffs_a [Ba][Ka][D][N] with times_a, side B coeffs_b
+    [Bb][Kb][D][N] with times_b (D = 3 or 4; both 'aos' [B][K] or both 'soa' [K][B]; the two sides may be the same tensors),
+    start_a [Ba] / start_b [Bb] the global time at which each trajectory starts (None: 0), pairs [P][2] int32 rows of (index into
+    A, index into B), see all_pairs -- CUDA tensors.  A pair fails iff not ||pA(t) - pB(t)|| - min_separation > 0 at a breakpoint of
+    either side or a critical point of the distance within the time both fly; a pair that never flies at the same time is feasible
+    with separation +inf.  A pair with an index out of range, a negative or non-finite segment time or a non-finite start is
+    infeasible with NaN separation.  include/mtg_hip.h has every rule."""
+    return _trajectory_separation(_SegmentBatch.device(ctx, coeffs_a, times_a, times_layout),
+                                  _SegmentBatch.device(ctx, coeffs_b, times_b, times_layout), pairs, min_separation, start_a, start_b,
+                                  want_closest)
+
+
+def check_trajectory_separation_host(coeffs_a, times_a, coeffs_b, times_b, pairs, min_separation: float, start_a=None, start_b=None,
+                                     times_layout: str = "aos", want_closest: bool = True) -> TrajectorySeparationResult:
+    """The same check on numpy arrays through the library's host build of the same code (no context, no device).  Here a pair index
+    out of range raises."""
+    return _trajectory_separation(_SegmentBatch.host(coeffs_a, times_a, times_layout), _SegmentBatch.host(coeffs_b, times_b, times_layout),
+                                  pairs, min_separation, start_a, start_b, want_closest)
 
 
 def keep_out_boxes(centers, sizes) -> np.ndarray:
