@@ -7,7 +7,8 @@
 // of spheres, what a caller of the reference loops offsetTrajectory + computeMinMaxMagnitude for, checkSeparation -- the distance
 // between pairs of trajectories over the time both fly, and checkKeepOutZones -- the same
 // question for convex zones (boxes, prisms) given as half spaces, and checkDistanceField -- a sampled check against a voxel grid of
-// distances (an ESDF), certifyDistanceField its certified form.  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
+// distances (an ESDF), certifyDistanceField its certified form, collisionCost the cost such a grid puts on a trajectory with its
+// gradient with respect to the coefficients.  Host code only: device memory goes through mtg_device_malloc / mtg_copy_*.
 // The single-trajectory functions stay on the host (trajectory.h); this class is for B >> 1.
 #ifndef MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
 #define MAV_TRAJECTORY_GENERATION_TRAJECTORY_BATCH_H_
@@ -360,6 +361,39 @@ class TrajectoryBatch {
     return rc == MTG_OK;
   }
 
+  // The distance-field collision COST of every trajectory and its gradient with respect to the polynomial coefficients
+  // (mtg_collision_cost): the map term of a CHOMP-style objective, sum over the samples (local times 0, i dt < T and T, trapezoid
+  // weights w) of w c(distance(p(t)) - inflation) sqrt(|v(t)|^2 + speed_epsilon^2), c the CHOMP potential that vanishes at a clearance
+  // of epsilon.  field.distances is a DEVICE pointer (DeviceDistanceField), the field trilinear.  trajectory_cost [B];
+  // coeff_gradient [B][K][D][N] in the layout of the coefficients (the exact derivative of the sum; yaw rows 0); segment_cost
+  // [B][K] (NaN: a segment with more than max_samples samples).  The outputs are optional; without coeff_gradient the kernel
+  // without the gradient runs.  false: arguments the call refuses (include/mtg_hip.h).
+  bool collisionCost(const mtg_distance_field& field, double dt, double inflation, double epsilon, double speed_epsilon,
+                     std::vector<double>* trajectory_cost, std::vector<double>* coeff_gradient = nullptr,
+                     std::vector<double>* segment_cost = nullptr, int max_samples = 4096) {
+    const size_t n_seg = (size_t)B_ * K_, n_grad = coeff_gradient ? n_seg * D_ * N_ : 0;
+    double* d_out = (double*)dmalloc(sizeof(double) * (n_seg + B_ + n_grad));
+    const int rc = mtg_collision_cost(ctx(), N_, K_, D_, B_, coeffs_, times_, K_, 1, &field, dt, max_samples, inflation, epsilon,
+                                      speed_epsilon, d_out, d_out + n_seg, coeff_gradient ? d_out + n_seg + B_ : nullptr, nullptr);
+    if (rc == MTG_OK) {
+      if (segment_cost) {
+        segment_cost->resize(n_seg);
+        check(mtg_copy_to_host(ctx(), segment_cost->data(), d_out, sizeof(double) * n_seg));
+      }
+      if (trajectory_cost) {
+        trajectory_cost->resize(B_);
+        check(mtg_copy_to_host(ctx(), trajectory_cost->data(), d_out + n_seg, sizeof(double) * B_));
+      }
+      if (coeff_gradient) {
+        coeff_gradient->resize(n_grad);
+        check(mtg_copy_to_host(ctx(), coeff_gradient->data(), d_out + n_seg + B_, sizeof(double) * n_grad));
+      }
+    }
+    mtg_device_free(ctx(), d_out);
+    if (rc != MTG_OK && rc != MTG_ERR_INVALID_ARGUMENT) check(rc);
+    return rc == MTG_OK;
+  }
+
   // In place on the device copy; returns true when every trajectory ended within range.
   bool scaleSegmentTimesToMeetConstraints(double v_max, double a_max, std::vector<char>* within_range = nullptr,
                                           std::vector<double>* scaling = nullptr) {
@@ -690,6 +724,43 @@ inline int mtgCertifyDistanceField(const Trajectory& trajectory, const mtg_dista
   if (lower_bound) *lower_bound = lower;
   if (sampled_clearance) *sampled_clearance = sampled;
   return result;
+}
+
+// TrajectoryBatch::collisionCost on a DeviceDistanceField (the device copy of a host grid).
+inline bool mtgCollisionCost(TrajectoryBatch& batch, const DeviceDistanceField& field, double dt, double inflation, double epsilon,
+                             double speed_epsilon, std::vector<double>* trajectory_cost, std::vector<double>* coeff_gradient = nullptr,
+                             std::vector<double>* segment_cost = nullptr, int max_samples = 4096) {
+  return batch.collisionCost(field.field(), dt, inflation, epsilon, speed_epsilon, trajectory_cost, coeff_gradient, segment_cost, max_samples);
+}
+
+// One trajectory's distance-field collision cost and gradient on the HOST (mtg_collision_cost_host: no device, no context; the
+// same order of every sum as the device form).  field.distances is a host pointer, the field trilinear.  Returns the trajectory's
+// cost; coeff_gradient [K][D][N] (the layout of the segments' coefficients) and segment_cost [K] are optional.  Arguments the call
+// refuses (include/mtg_hip.h): NaN, and the two vectors are emptied.
+inline double mtgCollisionCost(const Trajectory& trajectory, const mtg_distance_field& field, double dt, double inflation, double epsilon,
+                               double speed_epsilon = 1e-3, std::vector<double>* coeff_gradient = nullptr,
+                               std::vector<double>* segment_cost = nullptr, int max_samples = 4096) {
+  const int n = trajectory.N(), k = trajectory.K(), dim = trajectory.D();
+  std::vector<double> c((size_t)k * dim * n), t((size_t)k), seg((size_t)k);
+  for (int s = 0; s < k; ++s) {
+    const Segment& segment = trajectory.segments()[s];
+    t[s] = segment.getTime();
+    for (int d = 0; d < dim; ++d) {
+      const Eigen::VectorXd v = segment[d].getCoefficients();
+      for (int i = 0; i < n; ++i) c[((size_t)s * dim + d) * n + i] = v[i];
+    }
+  }
+  double total = std::nan("");
+  if (coeff_gradient) coeff_gradient->assign(c.size(), 0.0);
+  const int rc = mtg_collision_cost_host(n, k, dim, 1, c.data(), t.data(), k, 1, &field, dt, max_samples, inflation, epsilon, speed_epsilon,
+                                         seg.data(), &total, coeff_gradient ? coeff_gradient->data() : nullptr, nullptr);
+  if (rc != MTG_OK) {
+    total = std::nan("");
+    seg.clear();
+    if (coeff_gradient) coeff_gradient->clear();
+  }
+  if (segment_cost) *segment_cost = seg;
+  return total;
 }
 
 }  // namespace mav_trajectory_generation

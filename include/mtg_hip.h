@@ -894,6 +894,63 @@ int mtg_certify_distance_field_host(int32_t n_coeffs, int32_t n_segments, int32_
  * (which the check refuses).  Reads distances, nx, ny, nz (each >= 2) and voxel_size only.  */
 int mtg_distance_field_lipschitz_host(const mtg_distance_field* field, double* out);
 
+/* ---- next to the distance-field checks: collision COST and its gradient ---------------------------
+ * The map term of the CHOMP / continuous-time replanning objective  J_collision = sum over the segments of
+ * int c(d(p(t)) - inflation) ||v(t)|| dt,  as a trapezoid sum on the sample grid of mtg_check_distance_field, and the exact
+ * derivative of that sum with respect to every polynomial coefficient (same layout as coeffs).  Shape, times, field, dt,
+ * max_samples and inflation are those of mtg_check_distance_field; the field must be TRILINEAR (a nearest-voxel field has a zero
+ * gradient almost everywhere).  epsilon > 0, finite: the clearance at which the cost vanishes.  speed_epsilon >= 0, finite: the
+ * smoothing of the speed, which makes the gradient well defined where the vehicle rests.
+ * Every rounding is fixed so that a host loop reproduces each choice; fl() rounds once, every fma is fused, nothing else is:
+ *   samples    the field check's: t_0 = 0, t_i = fl(i dt) for i >= 1 with fl(i dt) < T, then T; S of them.  S > max_samples: the
+ *              segment is not sampled: segment_cost NaN, its gradient entries NaN, segment_samples -1.
+ *   weights    w_0 = fl(fl(t_1 - t_0) 0.5),  w_i = fl(fl(t_{i+1} - t_{i-1}) 0.5),  w_{S-1} = fl(fl(t_{S-1} - t_{S-2}) 0.5).
+ *              T <= 0: every weight is 0 (cost 0, gradient 0, S = 2).  T NaN: the weights, the cost and the gradient are NaN.
+ *   p, v       dimensions 0-2, one pass per axis from the highest coefficient down, both from 0:
+ *              v = fma(v, t, p); p = fma(p, t, c_j).  A 4th (yaw) dimension is never read; its N gradient entries are 0 in every
+ *              segment (also one that is not sampled or has a NaN time).
+ *   d          the field check's u_a and trilinear lookup, operation for operation
+ *   G          the field's gradient from the lookup's own eight voxels, f_a, x00 .. x11, y0, y1 and r, inside the grid only.  With
+ *              lerp_a(lo, hi) = fma(f_a, fl(hi - lo), lo) and e00, e10, e01, e11 the four (hi - lo) x-differences:
+ *              G_x = fl(r lerp_z(lerp_y(e00, e10), lerp_y(e01, e11))),  G_y = fl(r lerp_z(fl(x10 - x00), fl(x11 - x01))),
+ *              G_z = fl(r fl(y1 - y0)).  Outside: d = outside_distance, G = 0.  A NaN u_a: d and G are NaN.
+ *   potential  x = fl(d - inflation).  x < 0: c = fl(fl(epsilon 0.5) - x), c' = -1.  0 <= x <= epsilon: q = fl(x - epsilon),
+ *              c = fl(fl(q q) / fl(2 epsilon)), c' = fl(q / epsilon).  x > epsilon: c = c' = 0, and the sample is SKIPPED: it adds
+ *              nothing to any sum, whatever its speed and G are.  x NaN: c = c' = NaN.  (The CHOMP potential: c, c' continuous.)
+ *   speed      s = sqrt(fma(v_z, v_z, fma(v_y, v_y, fma(v_x, v_x, fl(speed_epsilon^2)))))
+ *   cost       a sample's term is fl(fl(w c) s); a segment's cost is the sum of its terms
+ *   gradient   the exact derivative of that sum,  d/dc_{a,j} = sum_i [ (w c' s G_a) t^j + (w c / s v_a) j t^(j-1) ]:
+ *              k1 = fl(fl(w c') s), A_a = fl(k1 G_a);  k2 = fl(fl(w c) / s), 0 if s == 0, B_a = fl(k2 v_a);
+ *              q_0 = 1, q_j = fl(q_{j-1} t);  entry (a, j): acc = fma(A_a, q_j, acc), then for j >= 1
+ *              acc = fma(B_a, fl(j q_{j-1}), acc)
+ *   sums       every segment sum is 64 partial sums from +0: partial g takes samples g, g + 64, .. in ascending order; they are
+ *              joined by the butterfly P[l] = fl(P[l] + P[l xor off]) for off = 32, 16, 8, 4, 2, 1.  The host form does the same.
+ *   trajectory trajectory_cost = the sum of segment_cost over the segments in ascending order, from +0, formed by a second kernel
+ *              from the written segment_cost (hence required).  No floating-point atomics anywhere.
+ * Non-finite voxels and outside_distance = +-infinity follow from this arithmetic.
+ *   segment_cost     out [batch][K]; required
+ *   trajectory_cost  out optional [batch]
+ *   coeff_gradient   out optional [batch][K][D][N], the layout of coeffs; without it a kernel without the gradient's registers runs
+ *                    and gives the same costs bit for bit
+ *   segment_samples  out optional [batch][K]: S, or -1 (not sampled)
+ * Device pointers; asynchronous on the context's stream, one launch (two with trajectory_cost), one wavefront per segment, no
+ * workspace, no allocation, no synchronisation, capturable.  The arguments are checked before the context (the argument rules
+ * need no device).  Argument errors (those of mtg_check_distance_field; a nearest field; epsilon not positive and finite;
+ * speed_epsilon negative or not finite; a null segment_cost): MTG_ERR_INVALID_ARGUMENT, nothing enqueued; batch == 0 returns
+ * before anything is.  Not provided: the derivative with respect to the segment times (the sample set changes with T).  */
+int mtg_collision_cost(mtg_context* ctx, int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                       const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                       const mtg_distance_field* field, double dt, int32_t max_samples, double inflation, double epsilon,
+                       double speed_epsilon, double* segment_cost, double* trajectory_cost, double* coeff_gradient,
+                       int32_t* segment_samples);
+/* The same with HOST pointers (field->distances too) on the library's host build of the same code, synchronous; needs no
+ * context and no device.  */
+int mtg_collision_cost_host(int32_t n_coeffs, int32_t n_segments, int32_t dimension, int64_t batch,
+                            const double* coeffs, const double* times, int64_t times_stride_b, int64_t times_stride_k,
+                            const mtg_distance_field* field, double dt, int32_t max_samples, double inflation, double epsilon,
+                            double speed_epsilon, double* segment_cost, double* trajectory_cost, double* coeff_gradient,
+                            int32_t* segment_samples);
+
 /* ---- the time optimisers' objective with soft constraints ---------------------------------------
  * Replaces, for a batch, the callbacks PolynomialOptimizationNonLinear<N> hands to nlopt
  * (impl/polynomial_optimization_nonlinear_impl.h, NL below): objectiveFunctionTime (NL:556-615) and

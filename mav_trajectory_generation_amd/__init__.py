@@ -32,10 +32,12 @@ _DISTANCE_FIELD = ("DistanceField", "DistanceFieldResult", "check_distance_field
 _CERTIFIED_FIELD = ("CertifiedFieldResult", "certify_distance_field", "certify_distance_field_host")
 # (and the trajectory-to-trajectory separation check)
 _SEPARATION = ("TrajectorySeparationResult", "check_trajectory_separation", "check_trajectory_separation_host", "all_pairs")
+# (and the distance-field collision cost and gradient)
+_COLLISION_COST = ("CollisionCostResult", "collision_cost", "collision_cost_host")
 
 
 def __getattr__(name):
-    if name in _KEEP_OUT or name in _DISTANCE_FIELD or name in _CERTIFIED_FIELD or name in _SEPARATION:
+    if name in _KEEP_OUT or name in _DISTANCE_FIELD or name in _CERTIFIED_FIELD or name in _SEPARATION or name in _COLLISION_COST:
         from . import segment_checks
         return getattr(segment_checks, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -173,6 +173,8 @@ EXPORTS = {
                                                     ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                     c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_void_p,
                                                     c_double_p, c_double_p]),
+    **_segment_entry("mtg_collision_cost", [ctypes.POINTER(DistanceFieldC), ctypes.c_double, ctypes.c_int32, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_double, c_double_p, c_double_p, c_double_p, ctypes.c_void_p]),
     "mtg_distance_field_lipschitz_host": (ctypes.c_int, [ctypes.POINTER(DistanceFieldC), ctypes.POINTER(ctypes.c_double)]),
     "mtg_time_objective_params_init":(None, [ctypes.POINTER(TimeObjectiveParamsC)]),
     "mtg_time_objective": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Layout), c_double_p, c_double_p, c_double_p,

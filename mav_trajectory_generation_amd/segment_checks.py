@@ -1,5 +1,6 @@
 """The batched per-segment calls: everything that takes a solved batch `coeffs [B][K][D][N]` with strided `times` -- sampling,
-extrema, time scaling, the input-feasibility, half-plane, obstacle, separation and distance-field checks and the time objective's soft cost -- in the device
+extrema, time scaling, the input-feasibility, half-plane, obstacle, separation and distance-field checks, the distance-field
+collision cost and the time objective's soft cost -- in the device
 form (CUDA tensors, a Context) and the host form (numpy, the library's host build of the same lane code).
 
 This is the Python half of the frame the C++ side has in csrc/mtg_segment_lane.h / mtg_segment_kernel.h: _SegmentBatch validates
@@ -887,6 +888,50 @@ def certify_distance_field_host(coeffs, times, field: DistanceField, lipschitz: 
     [B][K][D][N] or one trajectory [K][D][N] (results then without the batch axis); field.distances a float32 numpy array."""
     return _certify_distance_field(_SegmentBatch.host(coeffs, times, times_layout), field, lipschitz, inflation, min_depth, max_depth,
                                    max_frontier, True)
+
+
+class CollisionCostResult(NamedTuple):
+    """trajectory_cost [B] (sum of segment_cost in segment order), segment_cost [B][K] (sum over the samples of w c(d - inflation) s;
+    NaN: not sampled), coeff_gradient [B][K][D][N] (the exact derivative of segment_cost with respect to coeffs, the yaw rows 0) or
+    None, segment_samples [B][K] int32 (S; -1: more than max_samples, not sampled)."""
+    trajectory_cost: object
+    segment_cost: object
+    coeff_gradient: object
+    segment_samples: object
+
+
+def _collision_cost(b: _SegmentBatch, field, dt, inflation, epsilon, speed_epsilon, max_samples, want_gradient) -> CollisionCostResult:
+    grid, c = _field_struct(b, field)
+    traj = b.empty((b.B,), b.f64)
+    seg = b.empty((b.B, b.K), b.f64)
+    grad = b.empty((b.B, b.K, b.D, b.N), b.f64, want_gradient)
+    seg_s = b.empty((b.B, b.K), b.i32)
+    b.call("mtg_collision_cost", ctypes.byref(c), float(dt), int(max_samples), float(inflation), float(epsilon), float(speed_epsilon),
+           seg, traj, grad, seg_s)
+    return b.result((traj, seg, grad, seg_s), CollisionCostResult._make)
+
+
+def collision_cost(ctx: "Context", coeffs, times, field: DistanceField, dt: float, *, inflation: float = 0.0, epsilon: float,
+                   speed_epsilon: float = 1e-3, max_samples: int = 4096, want_gradient: bool = True,
+                   times_layout: str = "aos") -> CollisionCostResult:
+    """Batched distance-field collision cost of solved trajectories and its gradient with respect to the polynomial coefficients,
+    the map term of a CHOMP-style objective: coeffs [B][K][D][N] (D = 3 or 4), times ([B][K] 'aos' / [K][B] 'soa') as CUDA float64
+    tensors, field a trilinear DistanceField whose distances are a float32 CUDA tensor.  Every segment is sampled at local times 0,
+    i dt < T and T with trapezoid weights w; a sample adds w c(d(p) - inflation) sqrt(|v|^2 + speed_epsilon^2) with the CHOMP potential
+    c (epsilon / 2 - x below 0, (x - epsilon)^2 / (2 epsilon) up to epsilon, 0 beyond).  The gradient is the exact derivative of
+    that sum.  A segment with more than max_samples samples is not sampled: NaN.  include/mtg_hip.h has every rule."""
+    return _collision_cost(_SegmentBatch.device(ctx, coeffs, times, times_layout), field, dt, inflation, epsilon, speed_epsilon,
+                           max_samples, want_gradient)
+
+
+def collision_cost_host(coeffs, times, field: DistanceField, dt: float, *, inflation: float = 0.0, epsilon: float,
+                        speed_epsilon: float = 1e-3, max_samples: int = 4096, want_gradient: bool = True,
+                        times_layout: str = "aos") -> CollisionCostResult:
+    """The same on numpy arrays through the library's host build of the same code, with the device's order of every sum (no
+    context, no device): coeffs [B][K][D][N] or one trajectory [K][D][N] (results then without the batch axis); field.distances a
+    float32 numpy array."""
+    return _collision_cost(_SegmentBatch.host(coeffs, times, times_layout), field, dt, inflation, epsilon, speed_epsilon, max_samples,
+                           want_gradient)
 
 
 def _magnitude_soft_cost(b: _SegmentBatch, params):
