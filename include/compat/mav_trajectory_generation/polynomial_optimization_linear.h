@@ -605,6 +605,36 @@ class PolynomialOptimizationBatch {
     CHECK(rc == MTG_OK) << mtg_status_string(rc) << " " << mtg_last_error_string(mtg_plan_context(plan_.get()));
     return true;
   }
+  // Gradient with respect to the free derivatives (new API; the reference has none, polynomial_optimization_nonlinear.h:215-243):
+  // the transpose of the map d_free -> coefficients applied to grad_coeffs [B][K][D][N] (may be null), plus, with coeffs
+  // [B][K][D][N] given, smoothness_weight times the gradient Q(T) c of the cost solveLinear() minimises.  grad_free
+  // [B][D][n_free], grad_fixed [B][D][n_fixed] (either may be null, not both).  Device pointers: mtg_free_gradient,
+  // asynchronous.  Host pointers: mtg_free_gradient_host on the library's host build of the same code, synchronous and bit-identical.
+  void freeGradient(size_t batch, const double* times, const double* grad_coeffs, const double* coeffs, double smoothness_weight,
+                    double* grad_free, double* grad_fixed = nullptr, bool device_pointers = false) {
+    if (!device_pointers) {
+      freeGradientHost(dimension_, mask_, derivative_, batch, times, grad_coeffs, coeffs, smoothness_weight, grad_free, grad_fixed);
+      return;
+    }
+    mtg_layout lay;
+    mtg_layout_aos(plan_.get(), (int64_t)batch, &lay);
+    const int rc = mtg_free_gradient(plan_.get(), (int64_t)batch, &lay, times, grad_coeffs, coeffs, smoothness_weight, grad_free, grad_fixed);
+    CHECK(rc == MTG_OK) << mtg_status_string(rc) << " " << mtg_last_error_string(mtg_plan_context(plan_.get()));
+  }
+  // The host form without an object: needs no plan, no context and no device.
+  static void freeGradientHost(size_t dimension, const std::vector<uint32_t>& fixed_mask, int derivative_to_optimize, size_t batch,
+                               const double* times, const double* grad_coeffs, const double* coeffs, double smoothness_weight,
+                               double* grad_free, double* grad_fixed = nullptr) {
+    CHECK(fixed_mask.size() >= 2) << "fixed_mask needs n_segments + 1 entries";
+    const int64_t K = (int64_t)fixed_mask.size() - 1, D = (int64_t)dimension;
+    int64_t n_fixed = 0;
+    for (uint32_t m : fixed_mask) n_fixed += __builtin_popcount(m & ((1u << (N / 2)) - 1u));
+    const int64_t n_free = (N / 2) * (K + 1) - n_fixed;
+    const mtg_layout lay{K, 1, D * n_fixed, n_fixed, 1, D * n_free, n_free, 1};
+    const mtg_plan_desc desc{N, (int32_t)D, (int32_t)K, derivative_to_optimize, fixed_mask.data()};
+    const int rc = mtg_free_gradient_host(&desc, (int64_t)batch, &lay, times, grad_coeffs, coeffs, smoothness_weight, grad_free, grad_fixed);
+    CHECK(rc == MTG_OK) << mtg_status_string(rc);
+  }
   // waits for the device-pointer solves of THIS object (the context its plan was created on, whichever thread calls)
   void sync() { mtg_compat_detail::check_sync(plan_.get()); }
 

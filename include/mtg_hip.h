@@ -951,6 +951,53 @@ int mtg_collision_cost_host(int32_t n_coeffs, int32_t n_segments, int32_t dimens
                             double speed_epsilon, double* segment_cost, double* trajectory_cost, double* coeff_gradient,
                             int32_t* segment_samples);
 
+/* ---- gradient with respect to the free derivatives: the transpose of mtg_update_segments_from_free ----
+ * What an optimiser moves are the free derivatives d_free; the coefficients are a linear image of them,
+ * c = A(T)^-1 M [d_F; d_P].  This call applies the exact transpose of that map to a coefficient-space gradient
+ * G [batch][K][D][N] (the layout of coeffs; e.g. mtg_collision_cost's coeff_gradient) and, with coeffs given, adds the
+ * derivative cost's gradient w Q(T) c (the cost mtg_solve_linear reports is 0.5 sum c^T Q(T) c, LIN:124-140) on the fly.
+ * The reference has no such gradient (polynomial_optimization_nonlinear.h:215-243: gradient-free methods only).
+ * Forward map per segment (time T) and dimension, h = N/2, x_S / x_E the derivative values at the segment's start / end
+ * vertex, ai = rows h .. N-1 of A(1)^-1:   c_p = x_S,p / p!  (p < h),   c_(h+j) = T^-(h+j) sum_k ai[j][k] dl_k,
+ * dl = [T^p x_S,p ; T^p x_E,p].  Every rounding is fixed so that a host loop reproduces each bit; fl() rounds once, every fma
+ * is fused, nothing else is (contraction off); nothing depends on the launch geometry, and the device and host forms agree bit
+ * for bit:
+ *   powers     tp_0 = 1, tp_m = fl(tp_(m-1) T);  ti = fl(1 / T), tn_1 = ti, tn_m = fl(tn_(m-1) ti): repeated multiplication
+ *              from T and ONE division
+ *   input      G_i = grad_coeffs entry i of the row of (segment, dimension), +0 without grad_coeffs.  With coeffs, for
+ *              i >= d = derivative_to_optimize:  y_j = fl(c_j tp_(j-d)) (j >= d),  S_i = the sum over j = d .. N-1 in
+ *              ascending order, one fma(Q1[i][j], y_j, S) per term from +0 (Q1 = Q(1), the library's table),
+ *              q_i = fl(tp_(i-d+1) S_i)  [(Q(T) c)_i = T^(1-2d) T^i sum_j Q1_ij c_j T^j with the powers joined: no division],
+ *              G_i = fma(w, q_i, G_i).  Rows i < d of Q are zero: G_i stays as it is, whatever w is.
+ *   u          u_j = fl(tn_(h+j) G_(h+j)),  j < h
+ *   z          z_k = the sum over j = 0 .. h-1 in ascending order, one fma(ai[j][k], u_j, z) per term from +0
+ *   halves     start vertex: g_S,p = fma(tp_p, z_p, fl(G_p rf_p)), rf_p = fl(1 / p!);  end vertex: g_E,p = fl(tp_p z_(h+p))
+ *   vertex     0 < v < K: fl(g_E,p of segment v - 1  +  g_S,p of segment v): the left segment's end first, ONE rounded
+ *              addition;  v = 0: g_S,p of segment 0;  v = K: g_E,p of segment K - 1
+ *   routing    fixed_mask[v] bit p set: grad_fixed, the column of (v, p) in the order of d_fixed; else grad_free, the column
+ *              of (v, p) in the order of d_free.  Every output element is written exactly once.
+ * Times are NOT validated: T <= 0 or a NaN T gives what this arithmetic gives (ti = fl(1 / T) is infinite or NaN); no status
+ * word is raised, other trajectories are unaffected.
+ *   grad_coeffs        in  [batch][K][D][N] or NULL (treated as +0)
+ *   coeffs             in  [batch][K][D][N] or NULL: no derivative-cost term, smoothness_weight is ignored
+ *   grad_free          out layout's free strides (grad_free[b*free_stride_b + dim*free_stride_d + col*free_stride_c]); NULL: not wanted
+ *   grad_fixed         out optional, layout's fixed strides
+ * At least one of grad_coeffs / coeffs and at least one of grad_free / grad_fixed must be given (with n_free == 0 grad_free
+ * may be NULL and is never written).  The map is linear and needs no factorisation: structurally rank-deficient plans are
+ * accepted like any other, no shadow plan is involved.
+ * Device pointers; asynchronous on the context's stream, ONE launch (one lane per trajectory, vertex and dimension), no
+ * workspace, no allocation, no floating-point atomics, capturable.  The arguments are checked before the context is used.
+ * Argument errors (a null plan, layout or times; a negative batch; both inputs or both outputs null; more than 2^31 - 1
+ * lanes): MTG_ERR_INVALID_ARGUMENT, nothing enqueued.  */
+int mtg_free_gradient(mtg_plan* plan, int64_t batch, const mtg_layout* layout, const double* times,
+                      const double* grad_coeffs, const double* coeffs, double smoothness_weight,
+                      double* grad_free, double* grad_fixed);
+/* The same with HOST pointers on the library's host build of the same code, synchronous; needs no context and no device:
+ * the masks and columns are derived from desc (the rules of mtg_plan_create: N even in 2 .. 12, D, K >= 1, d < N/2).  */
+int mtg_free_gradient_host(const mtg_plan_desc* desc, int64_t batch, const mtg_layout* layout, const double* times,
+                           const double* grad_coeffs, const double* coeffs, double smoothness_weight,
+                           double* grad_free, double* grad_fixed);
+
 /* ---- the time optimisers' objective with soft constraints ---------------------------------------
  * Replaces, for a batch, the callbacks PolynomialOptimizationNonLinear<N> hands to nlopt
  * (impl/polynomial_optimization_nonlinear_impl.h, NL below): objectiveFunctionTime (NL:556-615) and

@@ -35,8 +35,14 @@ _SEPARATION = ("TrajectorySeparationResult", "check_trajectory_separation", "che
 # (and the distance-field collision cost and gradient)
 _COLLISION_COST = ("CollisionCostResult", "collision_cost", "collision_cost_host")
 
+# (and the gradient with respect to the free derivatives: Plan.free_gradient is a method; the host form lives in core.py)
+_FREE_GRADIENT = ("free_gradient_host",)
+
 
 def __getattr__(name):
+    if name in _FREE_GRADIENT:
+        from . import core
+        return getattr(core, name)
     if name in _KEEP_OUT or name in _DISTANCE_FIELD or name in _CERTIFIED_FIELD or name in _SEPARATION or name in _COLLISION_COST:
         from . import segment_checks
         return getattr(segment_checks, name)

@@ -137,6 +137,10 @@ EXPORTS = {
     "mtg_device_group_gather_coeffs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "mtg_update_segments_from_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Layout), c_double_p,
                                                      c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_uint32]),
+    "mtg_free_gradient": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Layout), c_double_p, c_double_p, c_double_p,
+                                         ctypes.c_double, c_double_p, c_double_p]),
+    "mtg_free_gradient_host": (ctypes.c_int, [ctypes.POINTER(PlanDesc), ctypes.c_int64, ctypes.POINTER(Layout), c_double_p, c_double_p,
+                                              c_double_p, ctypes.c_double, c_double_p, c_double_p]),
     "mtg_device_malloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
     "mtg_device_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mtg_copy_to_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),

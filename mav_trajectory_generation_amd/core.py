@@ -311,6 +311,38 @@ class Plan:
         _check(self.lib, rc, self.ctx.handle)
         return coeffs, cost
 
+    def free_gradient(self, times, grad_coeffs=None, coeffs=None, smoothness_weight: float = 1.0, layout: str = "aos",
+                      want_fixed: bool = False):
+        """Gradient with respect to the free derivatives (mtg_free_gradient): the transpose of update_from_free applied to a
+        coefficient-space gradient grad_coeffs [B][K][D][N] (e.g. collision_cost's coeff_gradient), plus, with coeffs
+        [B][K][D][N] given, smoothness_weight times the derivative cost's gradient Q(T) c.  times in `layout`; float64 CUDA
+        tensors.  Returns (grad_free, grad_fixed) in the layout of d_free / d_fixed ('aos': [B][D][n]; 'soa': [D][n][B]);
+        grad_fixed is None unless want_fixed.  Times are not validated.  Asynchronous; one launch."""
+        import torch
+        if layout not in ("aos", "soa"):
+            raise ValueError(layout)
+        if grad_coeffs is None and coeffs is None:
+            raise MtgError(-1, "free_gradient needs grad_coeffs, coeffs or both")
+        for name, t in (("times", times), ("grad_coeffs", grad_coeffs), ("coeffs", coeffs)):
+            if t is not None and not (t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()):
+                raise MtgError(-1, name + " must be a contiguous float64 CUDA tensor")
+        if times.dim() != 2 or times.shape[1 if layout == "aos" else 0] != self.K:
+            raise MtgError(-1, "times must be [B][K] ('aos') or [K][B] ('soa')")
+        batch = times.shape[0] if layout == "aos" else times.shape[1]
+        for name, t in (("grad_coeffs", grad_coeffs), ("coeffs", coeffs)):
+            if t is not None and tuple(t.shape) != (batch, self.K, self.D, self.N):
+                raise MtgError(-1, name + " must be [B][K][D][N]")
+        shape = (lambda n: (batch, self.D, n)) if layout == "aos" else (lambda n: (self.D, n, batch))
+        grad_free = torch.empty(shape(self.n_free), dtype=torch.float64, device=times.device)
+        grad_fixed = torch.empty(shape(self.n_fixed), dtype=torch.float64, device=times.device) if want_fixed else None
+        lay = self.layout(batch, layout)
+        cur = self.ctx._enter()
+        rc = self.lib.mtg_free_gradient(self.handle, batch, ctypes.byref(lay), self._ptr(times), self._ptr(grad_coeffs),
+                                        self._ptr(coeffs), float(smoothness_weight), self._ptr(grad_free), self._ptr(grad_fixed))
+        self.ctx._leave(cur)
+        _check(self.lib, rc, self.ctx.handle)
+        return grad_free, grad_fixed
+
     def solve_host(self, times: np.ndarray, d_fixed: np.ndarray, want_free=True, want_cost=True, generic=False,
                    coeffs: Optional[np.ndarray] = None, host_backend: bool = False, basic_solution: bool = False):
         """Host-buffer convenience (AoS numpy in/out, staged through the device by the library).  Pass page-locked
@@ -500,6 +532,52 @@ class MultiSolve:
             self.close()
         except Exception:
             pass
+
+
+def free_gradient_host(n_coeffs, derivative, fixed_mask, times: np.ndarray, grad_coeffs: Optional[np.ndarray] = None,
+                       coeffs: Optional[np.ndarray] = None, smoothness_weight: float = 1.0, layout: str = "aos",
+                       want_fixed: bool = False, dimension: Optional[int] = None):
+    """Plan.free_gradient on numpy arrays through the library's host build of the same lane code (mtg_free_gradient_host: no
+    context, no device; bit-identical to the device form).  fixed_mask [K + 1]; times [B][K] ('aos') or [K][B] ('soa');
+    grad_coeffs / coeffs [B][K][D][N] (at least one).  Returns (grad_free, grad_fixed): [B][D][n] ('aos') or [D][n][B] ('soa'),
+    grad_fixed None unless want_fixed."""
+    if layout not in ("aos", "soa"):
+        raise ValueError(layout)
+    lib = L.load()
+    N, K = int(n_coeffs), len(fixed_mask) - 1
+    H = N // 2
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    if times.ndim != 2 or times.shape[1 if layout == "aos" else 0] != K:
+        raise MtgError(-1, "times must be [B][K] ('aos') or [K][B] ('soa') with K = len(fixed_mask) - 1")
+    batch = times.shape[0] if layout == "aos" else times.shape[1]
+    given = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (grad_coeffs, coeffs)]
+    if given[0] is None and given[1] is None:
+        raise MtgError(-1, "free_gradient_host needs grad_coeffs, coeffs or both")
+    D = int(dimension) if dimension is not None else next(a for a in given if a is not None).shape[2]
+    for a in given:
+        if a is not None and tuple(a.shape) != (batch, K, D, N):
+            raise MtgError(-1, "grad_coeffs / coeffs must be [B][K][D][N]")
+    n_fixed = sum(bin(int(m) & ((1 << H) - 1)).count("1") for m in fixed_mask)
+    n_free = H * (K + 1) - n_fixed
+    lay = L.Layout()
+    if layout == "aos":
+        lay.times_stride_b, lay.times_stride_k = K, 1
+        lay.fixed_stride_b, lay.fixed_stride_d, lay.fixed_stride_c = D * n_fixed, n_fixed, 1
+        lay.free_stride_b, lay.free_stride_d, lay.free_stride_c = D * n_free, n_free, 1
+        shape = lambda n: (batch, D, n)
+    else:
+        lay.times_stride_b, lay.times_stride_k = 1, batch
+        lay.fixed_stride_b, lay.fixed_stride_d, lay.fixed_stride_c = 1, n_fixed * batch, batch
+        lay.free_stride_b, lay.free_stride_d, lay.free_stride_c = 1, n_free * batch, batch
+        shape = lambda n: (D, n, batch)
+    grad_free = np.empty(shape(max(n_free, 0)))
+    grad_fixed = np.empty(shape(n_fixed)) if want_fixed else None
+    arr = (ctypes.c_uint32 * (K + 1))(*[int(m) for m in fixed_mask])
+    desc = L.PlanDesc(N, D, K, H - 1 if derivative is None else int(derivative), arr)
+    p = lambda a: ctypes.c_void_p(0) if a is None else ctypes.c_void_p(a.ctypes.data)
+    _check(lib, lib.mtg_free_gradient_host(ctypes.byref(desc), batch, ctypes.byref(lay), p(times), p(given[0]), p(given[1]),
+                                           float(smoothness_weight), p(grad_free), p(grad_fixed)))
+    return grad_free, grad_fixed
 
 
 def solve_linear_batch(n_coeffs, derivative, fixed_mask, times: np.ndarray, d_fixed: np.ndarray, device: int = 0,

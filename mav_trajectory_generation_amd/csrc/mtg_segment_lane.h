@@ -79,7 +79,7 @@ constexpr int even_instance(int n_coeffs, int min_instance) { return n_coeffs <=
 // f(std::integral_constant<int, NC>) for NC = even_instance(n_coeffs, MIN) in {MIN, MIN + 2, .., 12}
 template <int MIN, int NC = MIN, class F>
 inline void with_instance(int n_coeffs, F&& f) {
-  static_assert(MIN >= 4 && MIN % 2 == 0 && NC <= mtgx::kMaxCoeffs, "instantiations are 4, 6, 8, 10, 12");
+  static_assert(MIN >= 2 && MIN % 2 == 0 && NC <= mtgx::kMaxCoeffs, "instantiations are (2,) 4, 6, 8, 10, 12");
   if constexpr (NC == mtgx::kMaxCoeffs) f(std::integral_constant<int, NC>{});
   else if (even_instance(n_coeffs, MIN) == NC) f(std::integral_constant<int, NC>{});
   else with_instance<MIN, NC + 2>(n_coeffs, f);
